@@ -15,8 +15,13 @@ averaged with RCCL all-reduce; value = pairs of all ranks / max-over-ranks time.
 ``--config 4`` adds the mDeBERTa-v3-base + LoRA lyrics encoder (configs[3], S=256; its
 roofline is the text encoder's token GEMMs).
 
-Extra fields: "roofline" for the dominant kernel (timed live with HIP events on the launch
-stream) and "cpu_baseline" (the fp32 CPU oracle timed on this host, rank 0 at N=1).
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step computed (``DIR/<name>.npy``); the
+inputs depend on the arguments alone, so two builds can be compared output for output.
+
+``--full`` adds the measurements that take runs of their own: "roofline" for the dominant kernel
+(timed live with HIP events on the launch stream) and "cpu_baseline" (the fp32 CPU oracle timed
+on this host, rank 0 at N=1; ``--skip-cpu`` leaves it out).  Without ``--full`` both are null.
 """
 from __future__ import annotations
 
@@ -43,6 +48,30 @@ V, L, D, H = 10136, 50, 128, 4
 N_GENDERS, N_COUNTRIES, N_USERS = 3, 64, 840
 PEAK_BF16_TFLOPS = 2500.0       # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+
+
+DUMP_BUDGET = 60 << 20          # bytes per --dump-outputs directory (the limit is 64 MB)
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: every tensor of ``arrays`` as ``out_dir/<name>.npy``, floating point as
+    float32 (float64 kept), integers as float64.  The arrays share DUMP_BUDGET equally; one
+    over its share is written as a fixed sample of its elements (indices drawn from seed 0,
+    ascending), so the same elements are compared from run to run."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        to = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() \
+            else torch.float32
+        cap = share // (8 if to == torch.float64 else 4)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(to).cpu().numpy())
 
 
 def synthetic_batches(n: int, B: int, seed: int, device):
@@ -541,8 +570,9 @@ def main_eval(args, world, rank, device):
             dist.barrier()
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
+        ranks = None
         for i in range(args.steps):
-            step(i)
+            ranks = step(i)
         torch.cuda.synchronize(device)
         if world > 1:
             dist.barrier()
@@ -552,8 +582,10 @@ def main_eval(args, world, rank, device):
             t = torch.tensor([el], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"ranks": ranks})
         roof = None
-        if rank == 0:                                    # top-K kernel, live, on its stream
+        if rank == 0 and args.full:                      # top-K kernel, live, on its stream
             u = model.get_user_embedding(batches[0]["history_ids"], batches[0]["history_mask"],
                                          batches[0]["user_gender"], batches[0]["user_country"])
             sc = rt.score_catalogue(u, items)
@@ -575,7 +607,7 @@ def main_eval(args, world, rank, device):
                     "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": read_traffic("topk_rows_kernel"),
                     "avg_us": round(sec * 1e6, 2), "bytes_per_launch": by}
     cpu = None
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and world == 1 and args.full and not args.skip_cpu:
         from oracle import two_tower_ref as ref
         from oracle import retrieval_ref as rr
         gc = torch.Generator().manual_seed(0)
@@ -631,8 +663,7 @@ def main_prep(args, world, rank, device):
               for _ in range(2)]
 
     def step(i):
-        mel(waves[i % 2])
-        cov(covers[i % 2])
+        return mel(waves[i % 2]), cov(covers[i % 2])
 
     for i in range(max(args.warmup, 1)):
         step(i)
@@ -641,8 +672,9 @@ def main_prep(args, world, rank, device):
         dist.barrier()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
+    out = (None, None)
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
@@ -652,8 +684,10 @@ def main_prep(args, world, rank, device):
         t = torch.tensor([el], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mel": out[0], "cover": out[1]})
     roof = None
-    if rank == 0:                                        # mel_power kernel, live, on its stream
+    if rank == 0 and args.full:                          # mel_power kernel, live, on its stream
         st = torch.cuda.current_stream(device)
         out = torch.empty(B, 128, 1 + N // 512, device=device)
         mel.power(waves[0], out)
@@ -673,7 +707,7 @@ def main_prep(args, world, rank, device):
                 "avg_us": round(sec * 1e6, 2), "bytes_per_launch": by,
                 "note": "frames overlap 4x (hop 512 of 2048): each sample is read by 4 workgroups"}
     cpu = None
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and world == 1 and args.full and not args.skip_cpu:
         from oracle import prep_ref as pr
         import numpy as np
         w = waves[0][:8].cpu().numpy()
@@ -789,7 +823,15 @@ def main():
     ap.add_argument("--no-capture-collectives", action="store_true",
                     help="data-parallel schedule: collectives between graph segments (host cuts) "
                          "instead of inside the step's graph")
-    ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline probes of the dominant "
+                         "kernels and time the CPU oracle (cpu_baseline); off by default, so a "
+                         "plain run does only what its headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all; rank 0's at --gpus N)")
+    ap.add_argument("--skip-cpu", action="store_true",
+                    help="with --full: leave the CPU oracle out")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     args = ap.parse_args()
     global D, pkg
@@ -866,6 +908,11 @@ def main():
     torch.cuda.synchronize(device)
     el = time.perf_counter() - t0
     step.check()                  # an id outside its table in any timed step raises here
+    if rank == 0 and args.dump_outputs:
+        # what the loop's caller holds after its last step: that step's loss and logits and
+        # the updated parameters (the flat fp32 buffer every module parameter is a view of)
+        dump_outputs(args.dump_outputs, {"loss": step.loss, "logits": step.logits,
+                                         "params": step.flat.data})
     if world > 1:
         t = torch.tensor([el], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -873,7 +920,7 @@ def main():
     mean_loss = float(step.loss_sum) / max(args.steps, 1)
 
     roof = roof_panel = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if cfg4:
             roof = probe_text_gemm(step, batches[0], device)
         elif cfg3:
@@ -885,7 +932,7 @@ def main():
             except Exception as exc:           # a probe must never sink the bench line
                 print(f"probe_panels: {exc!r}", file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and world == 1 and args.full and not args.skip_cpu:
         if cfg4:
             cpu = cpu_baseline_cfg4(2, args.cpu_budget)
         elif cfg3:

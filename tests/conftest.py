@@ -1,3 +1,4 @@
+import glob
 import importlib
 import os
 import sys
@@ -18,8 +19,14 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    """The arrays of tests/golden/<name>, with those of its continuation files
+    (<stem>.part1.npz, ...: tools/make_golden.save_golden keeps every file under 1 MiB)."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    out = {}
+    for path in [stem + ".npz"] + sorted(glob.glob(glob.escape(stem) + ".part*.npz")):
+        with np.load(path, allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def sub(d, prefix):

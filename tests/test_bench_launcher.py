@@ -64,6 +64,26 @@ def test_world_size_must_equal_gpus():
     assert "WORLD_SIZE=2 but --gpus 1" in p.stderr
 
 
+def test_dump_outputs_dtypes_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 for floating point (float64 kept), float64 for integers, non-tensors
+    left out; an array over its share of the budget is the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 4 * 100)       # 4 arrays, 100 float32 each
+    big = torch.arange(1000, dtype=torch.float32)
+    arrays = {"h": torch.ones(2, 3, dtype=torch.bfloat16), "d": torch.ones(5, dtype=torch.float64),
+              "i": torch.tensor([1, 2 ** 40]), "big": big, "none": None}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["big", "d", "h", "i"]
+    assert a["h"].dtype == np.float32 and a["h"].shape == (2, 3)
+    assert a["d"].dtype == np.float64 and a["i"].dtype == np.float64 and a["i"][1] == 2.0 ** 40
+    assert a["big"].shape == (100,) and np.all(np.diff(a["big"]) >= 0)
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(v.nbytes for v in a.values()) <= 4 * 4 * 100
+
+
 def test_gpus_n_parent_imports_no_package(tmp_path):
     """The --gpus N parent spawns before importing the package (which loads the HIP library):
     bench.py's module level holds no package import."""

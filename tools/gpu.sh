@@ -9,9 +9,9 @@
 #                                        -> gpurun_out/prof_TAG_step.txt (tools/step_profile.py)
 #   tools/gpu.sh pmc TAG CONFIG          FETCH_SIZE / WRITE_SIZE passes of `bench.py --config
 #                                        CONFIG` -> gpurun_out/traffic_TAG.json (tools/traffic.py)
-#   tools/gpu.sh bench-all TAG [cfgs]    bench lines of 2, 2d256, 3, 4, 5, eval, prep
+#   tools/gpu.sh bench-all TAG [cfgs]    bench --full lines of 2, 2d256, 3, 4, 5, eval, prep
 #   tools/gpu.sh ab PAIRS A B [...] [-- bench args]   alternate env settings ("N=V[,N=V]" or
-#                                        "-"), 200-step cfg-2 benches
+#                                        "-"), 200-step cfg-2 benches with the roofline probes
 #   tools/gpu.sh ddp TAG [bench args]   RCCL world-1 tests, then cfg-2 bench lines: single-process,
 #                                        forced DDP schedule with captured RCCL collectives, and
 #                                        with host cuts (-> gpurun_out/ddp_TAG_*.json)
@@ -24,6 +24,8 @@ set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+# where `final` keeps its --full bench line (its other steps write beside progress.txt)
+OUT=${TTMI_OUT:-$R/bench_out}
 note() { echo "[$(date +%T)] $*" | tee -a gpurun_out/progress.txt; }
 
 tests() {
@@ -78,10 +80,10 @@ bench_all() {
   [ -z "$cfgs" ] && cfgs="2 2d256 3 4 5 eval prep"
   for c in $cfgs; do
     case $c in
-      2d256) args="--config 2 --dim 256 --steps 50 --warmup 10" ;;
-      3) args="--config 3 --steps 20 --warmup 5" ;;
-      4) args="--config 4 --steps 10 --warmup 3" ;;
-      *) args="--config $c" ;;
+      2d256) args="--full --config 2 --dim 256 --steps 50 --warmup 10" ;;
+      3) args="--full --config 3 --steps 20 --warmup 5" ;;
+      4) args="--full --config 4 --steps 10 --warmup 3" ;;
+      *) args="--full --config $c" ;;
     esac
     timeout -k 10 600 python bench.py $args > gpurun_out/bench_${tag}_$c.jsonl 2> gpurun_out/bench_${tag}_$c.err \
       || { tail -20 gpurun_out/bench_${tag}_$c.err; return 1; }
@@ -101,7 +103,7 @@ ab() {
       envs=()
       [ "$s" != "-" ] && IFS=',' read -r -a envs <<< "$s"
       tag=$(echo "$s" | tr -c 'A-Za-z0-9_' '_')
-      env "${envs[@]}" timeout -k 10 300 python bench.py --skip-cpu --steps 200 --warmup 20 "${extra[@]}" \
+      env "${envs[@]}" timeout -k 10 300 python bench.py --full --skip-cpu --steps 200 --warmup 20 "${extra[@]}" \
         > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err || { tail -20 gpurun_out/ab_$tag.err; return 1; }
       python3 -c "import json;d=json.loads(open('gpurun_out/ab_$tag.json').read().strip().splitlines()[-1]);r=d.get('roofline') or {};print('$s', d['value'], d['ms_per_step'], r.get('avg_us'), r.get('frac'))"
     done
@@ -167,13 +169,15 @@ final() {
     > gpurun_out/${tag}_tests.log 2>&1 || { tail -30 gpurun_out/${tag}_tests.log; return 1; }
   tail -2 gpurun_out/${tag}_tests.log
   note "default bench under rocprofv3"
+  mkdir -p "$OUT"
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_bench_prof \
-    -o run -- python3 $R/bench.py) > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err \
-    || { tail -20 gpurun_out/${tag}_bench.err; return 1; }
-  tail -1 gpurun_out/${tag}_bench.json
+    -o run -- python3 $R/bench.py --full) > "$OUT/${tag}_bench.json" 2> "$OUT/${tag}_bench.err" \
+    || { tail -20 "$OUT/${tag}_bench.err"; return 1; }
+  tail -1 "$OUT/${tag}_bench.json"
   for c in "--dim 256" "--config 5" "--config 3" "--config 4"; do
     t=$(echo "$c" | tr -c 'A-Za-z0-9' '_')
     note "bench $c"
+    c="--full $c"
     timeout -k 10 400 python3 bench.py $c > gpurun_out/${tag}_bench$t.json 2> gpurun_out/${tag}_bench$t.err \
       || { tail -20 gpurun_out/${tag}_bench$t.err; return 1; }
     tail -1 gpurun_out/${tag}_bench$t.json

@@ -78,11 +78,37 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
+PART_BYTES = 1000000      # no committed file may pass 1 MiB
+
+
+def save_golden(path, arrays):
+    """np.savez_compressed(path, **arrays), except that a fixture over PART_BYTES continues in
+    ``<stem>.part1.npz``, ``<stem>.part2.npz``, ...: the arrays go, in order, into the current
+    file until the next one would not fit (sizes measured compressed).  conftest.load_golden
+    merges the parts again."""
+    import io
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: a})
+        n = buf.getbuffer().nbytes
+        assert n <= PART_BYTES, (k, n)
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += n
+    stem = path[:-len(".npz")]
+    for i, part in enumerate(parts):
+        np.savez_compressed(path if i == 0 else f"{stem}.part{i}.npz", **part)
+    return len(parts)
+
+
 def _save(name, **arrays):
     os.makedirs(OUT, exist_ok=True)
     path = os.path.join(OUT, name)
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, sum(a.nbytes for a in arrays.values()) // 1024, "KiB")
+    n = save_golden(path, arrays)
+    print("wrote", path, sum(a.nbytes for a in arrays.values()) // 1024, "KiB in", n, "file(s)")
 
 
 def user_tower_case(ut, name, V, D, L, B, H, n_g, n_c, lengths, left_pad=(), use_mask=True,

@@ -93,7 +93,8 @@ def main():
             z[f"g/{base}.bias"] = pd[base + ".bias"].grad.numpy()
     z["g/encoder.rel_embeddings.weight"] = pd["encoder.rel_embeddings.weight"].grad.numpy()
     out_path = os.path.join(ROOT, "tests", "golden", "deberta_tiny.npz")
-    np.savez_compressed(out_path, **z)
+    from tools.make_golden import save_golden
+    save_golden(out_path, z)
     print("wrote", out_path, "out", out.shape, "keys", len(z))
 
 
