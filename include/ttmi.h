@@ -514,6 +514,8 @@ int ttmi_sum_scaled(int n, const float* x, float scale, float* out, hipStream_t 
  *                 WGRAD writes torch's [Co][Cin][7][7] layout like mode 2.
  * w is the bf16 mirror from ttmi_conv_weight_prep: Wf = [Co][KH][KW][C] for FWD,
  * Wd = [Cin][KH][KW][Co] for DGRAD.  Every tensor must have < 2^31 elements.
+ * ABI 23: with ttmi_conv_desc.f32 = 1 the activations and mirrors are fp32 instead of bf16
+ * (modes 0-2; the field's comment below), for reference-parity numerics.
  * ---------------------------------------------------------------------------------- */
 #define TTMI_CONV_STAT_REPS 16
 typedef struct ttmi_conv_desc {
@@ -535,6 +537,12 @@ typedef struct ttmi_conv_desc {
    * ttmi_bn2d_bwd_reduce's, so ttmi_bn2d_bwd_apply(g, ...) completes the BatchNorm backward. */
   const void* bn_gate; const void* bn_x; const float* bn_mean; const float* bn_rstd;
   int64_t* bn_sums;
+  /* ABI 23: storage of x, dy, w, out (FWD / DGRAD) and addend.  0 = bf16 (every rule above);
+   * 1 = fp32 NHWC activations and fp32 mirrors (ttmi_conv_weight_prep_f32): the same three
+   * modes 0-2 and descriptor meaning on v_mfma_f32_16x16x4_f32 (exact fp32 products), the
+   * same colsum/colsumsq and WGRAD reduction, bit-reproducible.  Modes 3 / 4 and bn_sums
+   * have no fp32 kernel: such a descriptor is refused (TTMI_ERR_ARG), never launched. */
+  int f32;
 } ttmi_conv_desc;
 int ttmi_conv2d(const ttmi_conv_desc* d, hipStream_t stream);
 /* Bytes of WGRAD scratch ttmi_conv2d needs for this descriptor (0 for FWD/DGRAD; -1 on a bad
@@ -544,6 +552,9 @@ int64_t ttmi_conv2d_workspace(const ttmi_conv_desc* d);
  * likewise (wd may be NULL). w is torch's fp32 Conv2d.weight. */
 int ttmi_conv_weight_prep(int Co, int Cin, int Cp, int KH, int KW, const float* w, uint16_t* wf,
                           uint16_t* wd, hipStream_t stream);
+/* The same mirrors in fp32 (ABI 23), for ttmi_conv_desc.f32 = 1. */
+int ttmi_conv_weight_prep_f32(int Co, int Cin, int Cp, int KH, int KW, const float* w, float* wf,
+                              float* wd, hipStream_t stream);
 /* Every conv's mirrors in one launch (ABI 17): items[i] as ttmi_conv_weight_prep's arguments,
  * or (s2d = 1, KH = KW = 7) ttmi_stem_weight_prep's [Co][4][4][Cp] mirror (wd unused).  At
  * most TTMI_WPREP_MAX items per launch (more are split over launches). */
@@ -553,11 +564,16 @@ typedef struct ttmi_conv_wprep {
   const float* w;
   uint16_t* wf;
   uint16_t* wd;           /* may be NULL */
+  int f32;                /* ABI 23: 1 = wf / wd are fp32 mirrors (float*; s2d must be 0); the
+                           * same value in every item of a call */
 } ttmi_conv_wprep;
 int ttmi_conv_weight_prep_batch(int n, const ttmi_conv_wprep* items, hipStream_t stream);
 /* y = bf16 NHWC [N,H,W,Cp] of x fp32 NCHW [N,Cin,H,W] (channels >= Cin zero). */
 int ttmi_nchw_to_nhwc(int N, int Cin, int H, int W, int Cp, const float* x, uint16_t* y,
                       hipStream_t stream);
+/* y = fp32 NHWC (ABI 23), the fp32-storage mode's stem input. */
+int ttmi_nchw_to_nhwc_f32(int N, int Cin, int H, int W, int Cp, const float* x, float* y,
+                          hipStream_t stream);
 /* Space-to-depth stem input (ABI 17): y = bf16 [N][H/2][W/2][Cp] of x fp32 NCHW [N,Cin,H,W]
  * (H, W even), channel (ph·2 + pw)·Cin + ci = x[n][ci][2h+ph][2w+pw], channels >= 4·Cin zero
  * (Cp % 8 == 0).  Replaces the stem's ttmi_nchw_to_nhwc for conv modes 3 / 4. */
@@ -624,6 +640,32 @@ int ttmi_maxpool_bwd(int N, int H, int W, int C, int k, int stride, int pad, con
 int ttmi_avgpool_fwd(int N, int HW, int C, const uint16_t* x, uint16_t* y, hipStream_t stream);
 int ttmi_avgpool_bwd(int N, int HW, int C, const void* dy, int dy_dtype, const uint16_t* gate,
                      uint16_t* dx, hipStream_t stream);
+/* fp32 storage (ABI 23): the BatchNorm2d and pool entry points above over NHWC fp32
+ * activations — the reference-parity mode of the ResNet encoders (ttmi_conv_desc.f32 = 1).  The
+ * same arguments, arithmetic, fixed-point sums and reduction orders; only the activations
+ * (x, y, dy, dx, gate, residual, g_out) are float instead of bf16, so nothing is rounded to
+ * bf16 between layers.  The fused stem kernels (ttmi_stem_pool_*, ttmi_stem_s2d) have no fp32
+ * form: the fp32 mode runs ttmi_bn2d_fwd_f32(relu) + ttmi_maxpool_fwd_f32. */
+int ttmi_bn2d_fwd_f32(int64_t M, int C, const float* x, const int64_t* colsum, const int64_t* colsumsq,
+                      const float* w, const float* b, float eps, float momentum, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, const float* residual, int relu,
+                      float* y, float* save_mean, float* save_rstd, hipStream_t stream);
+int ttmi_bn2d_bwd_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                      const float* mean, const float* rstd, const float* w, int64_t* sums, float* g_out,
+                      float* dx, float* dw, float* db, hipStream_t stream);
+int ttmi_bn2d_bwd_reduce_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                             const float* mean, const float* rstd, int64_t* sums, float* g_out,
+                             hipStream_t stream);
+int ttmi_bn2d_bwd_apply_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                            const float* mean, const float* rstd, const float* w, const int64_t* sums,
+                            float* dx, float* dw, float* db, hipStream_t stream);
+int ttmi_maxpool_fwd_f32(int N, int H, int W, int C, int k, int stride, int pad, const float* x, float* y,
+                         uint8_t* idx, hipStream_t stream);
+int ttmi_maxpool_bwd_f32(int N, int H, int W, int C, int k, int stride, int pad, const float* dy,
+                         const uint8_t* idx, float* dx, hipStream_t stream);
+int ttmi_avgpool_fwd_f32(int N, int HW, int C, const float* x, float* y, hipStream_t stream);
+int ttmi_avgpool_bwd_f32(int N, int HW, int C, const void* dy, int dy_dtype, const float* gate, float* dx,
+                         hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused AdamW over flat fp32 buffers (torch.optim.AdamW defaults, train.py:302):

@@ -7,13 +7,26 @@ global average pool, fc), with the reference's replacements (audio conv1 takes 1
 fc → Linear(512, embedding_dim)) and torchvision's parameter names, so checkpoints map
 one-to-one.  BatchNorm2d runs in train mode on batch statistics, as in the reference.
 
-Data layout: NHWC bf16 activations; the 1/3-channel image goes to a space-to-depth layout
-(ttmi_stem_s2d: [N][H/2][W/2][8 or 16]) so the 7x7/2 stem runs as a 4x4/1 conv (K = 128 / 256
-instead of 392 padded taps); conv weights are used through bf16 mirrors (ttmi_conv_weight_prep);
-every conv's forward epilogue accumulates the BatchNorm column sums (int64 fixed point, so the
-statistics are bit-reproducible), so a conv + BN + ReLU (+ residual) is two launches; the stem's
-bn1 + ReLU + maxpool is one (ttmi_stem_pool_fwd, the 112x112 BN output never stored).  All
-parameters and grads stay fp32 (torch layouts).
+Two storage modes, chosen by ``dtype`` (ResNet18 / AudioEncoder / VisualEncoder /
+TabularEncoder / resnet18_fwd / tabular_fwd); parameters, grads and state_dict are fp32 torch
+layouts in both, so checkpoints interchange.
+
+dtype=torch.bfloat16 (default, the throughput mode): NHWC bf16 activations; an even-sized
+1/3-channel image goes to a space-to-depth layout (ttmi_stem_s2d: [N][H/2][W/2][8 or 16]) so
+the 7x7/2 stem runs as a 4x4/1 conv (K = 128 / 256 instead of 392 padded taps), an odd-sized one
+is zero-padded to 8 channels; conv weights are used through bf16 mirrors
+(ttmi_conv_weight_prep); every conv's forward epilogue accumulates the BatchNorm column sums
+(int64 fixed point, so the statistics are bit-reproducible), so a conv + BN + ReLU (+ residual)
+is two launches; the stem's bn1 + ReLU + maxpool is one (ttmi_stem_pool_fwd, the 112x112 BN
+output never stored); the BatchNorm backward reductions ride in the DGRAD epilogues.
+
+dtype=torch.float32 (the reference-parity mode: the reference indexes and evaluates without
+autocast): NHWC fp32 activations and fp32 mirrors on the fp32-MFMA conv tile
+(ttmi_conv_desc.f32), the same fixed-point BatchNorm statistics, an fp32 fc GEMM.  It takes the
+generic path for every image size — nchw_to_nhwc (8 padded channels) → conv → bn2d_fwd(relu) →
+maxpool_fwd, and in the backward maxpool_bwd → bn2d_bwd → WGRAD with every BatchNorm reduction
+as its own pass: the space-to-depth stem, the fused stem pool and the DGRAD-fused reduction
+exist in bf16 storage only.
 """
 from __future__ import annotations
 
@@ -28,6 +41,15 @@ from . import functional as F
 from . import ops
 
 Tensor = torch.Tensor
+
+DTYPES = (torch.bfloat16, torch.float32)      # activation storage modes of the encoders
+
+
+def check_dtype(dtype: torch.dtype, who: str) -> torch.dtype:
+    if dtype not in DTYPES:
+        raise TypeError(f"{who}: dtype must be torch.bfloat16 or torch.float32, got {dtype}")
+    return dtype
+
 
 LAYERS = (("layer1", 64, 64, 1), ("layer2", 64, 128, 2), ("layer3", 128, 256, 2),
           ("layer4", 256, 512, 2))
@@ -73,13 +95,13 @@ def resnet18_convs(in_ch: int) -> List[ConvSpec]:
 # ---------------------------------------------------------------------------- state
 @dataclass
 class ConvAct:
-    x: Tensor              # conv input (bf16 NHWC)
+    x: Tensor              # conv input (NHWC, bf16 or fp32: the mode's storage dtype)
     H: int
     W: int
-    y: Tensor              # conv output, pre-BN (bf16 NHWC)
+    y: Tensor              # conv output, pre-BN (NHWC)
     mean: Tensor
     rstd: Tensor
-    a: Optional[Tensor]    # BN output (after residual/ReLU when fused); None for the stem
+    a: Optional[Tensor]    # BN output (after residual/ReLU when fused); None for the fused stem
 
 
 @dataclass
@@ -87,30 +109,31 @@ class ResNetSaved:
     N: int
     acts: Dict[str, ConvAct] = field(default_factory=dict)
     pool_idx: Optional[Tensor] = None
-    feat: Optional[Tensor] = None          # pooled features bf16 [N, 512]
+    feat: Optional[Tensor] = None          # pooled features [N, 512]
     last: Optional[Tensor] = None          # last block output (avgpool input)
     mirrors: Optional[Dict[str, Tuple[Tensor, Optional[Tensor]]]] = None
     fc_w: Optional[Tensor] = None
 
 
-def weight_mirrors(P: Dict[str, Tensor], specs: List[ConvSpec], s2d: bool = True):
-    """bf16 GEMM mirrors (Wf for FWD, Wd for DGRAD) of every conv weight; the stem's as the
-    4x4 kernel over the space-to-depth input when ``s2d`` (ttmi_stem_weight_prep)."""
+def weight_mirrors(P: Dict[str, Tensor], specs: List[ConvSpec], s2d: bool = True,
+                   dtype: torch.dtype = torch.bfloat16):
+    """GEMM mirrors (Wf for FWD, Wd for DGRAD) of every conv weight in ``dtype``; the stem's as
+    the 4x4 kernel over the space-to-depth input when ``s2d`` (ttmi_stem_weight_prep, bf16)."""
     out, items = {}, []
     for sp in specs:
         w = P[sp.name].contiguous()
         dev = w.device
         if s2d and _is_stem(sp):
             cp = stem_s2d_cp(sp.cin)
-            wf = torch.empty(sp.cout, 4, 4, cp, device=dev, dtype=torch.bfloat16)
+            wf = torch.empty(sp.cout, 4, 4, cp, device=dev, dtype=dtype)
             items.append((w, cp, wf, None, True))
             out[sp.name] = (wf, None)
             continue
         cp = STEM_CP if sp.cin < 8 else sp.cin
-        wf = torch.empty(sp.cout, sp.k, sp.k, cp, device=dev, dtype=torch.bfloat16)
+        wf = torch.empty(sp.cout, sp.k, sp.k, cp, device=dev, dtype=dtype)
         wd = None
         if sp.cin >= 8:
-            wd = torch.empty(sp.cin, sp.k, sp.k, sp.cout, device=dev, dtype=torch.bfloat16)
+            wd = torch.empty(sp.cin, sp.k, sp.k, sp.cout, device=dev, dtype=dtype)
         items.append((w, cp, wf, wd, False))
         out[sp.name] = (wf, wd)
     ops.conv_weight_prep_batch(items)          # one launch for the whole network
@@ -123,7 +146,7 @@ def _conv_bn(P, bufs, sp: ConvSpec, x: Tensor, N: int, H: int, W: int, mirrors, 
     dev = x.device
     C = x.shape[-1]
     Ho, Wo = ops.conv_out_hw(H, W, sp.k, sp.stride, sp.pad)
-    y = torch.empty(N, Ho, Wo, sp.cout, device=dev, dtype=torch.bfloat16)
+    y = torch.empty(N, Ho, Wo, sp.cout, device=dev, dtype=x.dtype)
     cs = cq = None                       # eval: BN normalises with the running statistics
     if training:
         n = ops.CONV_STAT_REPS * sp.cout
@@ -142,10 +165,14 @@ def _conv_bn(P, bufs, sp: ConvSpec, x: Tensor, N: int, H: int, W: int, mirrors, 
 
 
 def resnet18_fwd(P: Dict[str, Tensor], x: Tensor, in_ch: int, bufs: Dict[str, Tensor],
-                 training: bool = True, fc_dtype: torch.dtype = torch.bfloat16):
+                 training: bool = True, fc_dtype: torch.dtype = torch.bfloat16,
+                 dtype: torch.dtype = torch.bfloat16):
     """torchvision resnet18.forward on x [N, in_ch, H, W] fp32 → [N, out] fp32.  training:
     BN on batch statistics (running stats updated when ``bufs`` holds them); otherwise BN on
-    ``bufs``' running statistics."""
+    ``bufs``' running statistics.  dtype: the activation / mirror storage (module docstring);
+    torch.float32 also runs the fc as an fp32 GEMM, whatever ``fc_dtype``."""
+    if check_dtype(dtype, "resnet18_fwd") == torch.float32:
+        return _resnet18_fwd_f32(P, x, in_ch, bufs, training)
     dev = x.device
     N, _, H, W = x.shape
     specs = resnet18_convs(in_ch)
@@ -183,7 +210,20 @@ def resnet18_fwd(P: Dict[str, Tensor], x: Tensor, in_ch: int, bufs: Dict[str, Te
                       num_batches=bufs.get(sp.bn + ".num_batches_tracked") if training else None)
     st.acts[sp.name] = ConvAct(x0, H, W, yc, mean, rstd, None)
     off = 2 * ops.CONV_STAT_REPS * sp.cout
-    H, W = Hp, Wp
+    y = _res_stages_fwd(P, bufs, specs, st, y, N, Hp, Wp, mirrors, stats, off, training)
+    feat = torch.empty(N, 512, device=dev, dtype=torch.bfloat16)
+    ops.avgpool_fwd(y, feat)
+    st.feat = feat
+    fc_w = P["fc.weight"]
+    st.fc_w = ops.cast_bf16(fc_w.contiguous(), torch.empty(fc_w.shape, device=dev, dtype=fc_dtype))
+    out = torch.empty(N, fc_w.shape[0], device=dev)
+    ops.linear(feat, st.fc_w, P["fc.bias"], out)
+    return out, st
+
+
+def _res_stages_fwd(P, bufs, specs, st: "ResNetSaved", y: Tensor, N: int, H: int, W: int, mirrors,
+                    stats: Optional[Tensor], off: int, training: bool) -> Tensor:
+    """layer1..layer4 on the pooled stem output y (either storage dtype); fills st.acts / st.last."""
     byname = {s.name: s for s in specs}
     for lname, _, _, _ in LAYERS:
         for bi in range(2):
@@ -205,20 +245,47 @@ def resnet18_fwd(P: Dict[str, Tensor], x: Tensor, in_ch: int, bufs: Dict[str, Te
             st.acts[c2.name] = a2
             y, H, W = a2.a, H1, W1
     st.last = y
-    feat = torch.empty(N, 512, device=dev, dtype=torch.bfloat16)
-    ops.avgpool_fwd(y, feat)
-    st.feat = feat
-    fc_w = P["fc.weight"]
-    st.fc_w = ops.cast_bf16(fc_w.contiguous(), torch.empty(fc_w.shape, device=dev, dtype=fc_dtype))
-    out = torch.empty(N, fc_w.shape[0], device=dev)
-    ops.linear(feat, st.fc_w, P["fc.bias"], out)
+    return y
+
+
+def _resnet18_fwd_f32(P: Dict[str, Tensor], x: Tensor, in_ch: int, bufs: Dict[str, Tensor],
+                      training: bool):
+    """resnet18_fwd in fp32 storage: the generic stem for every image size, nothing fused
+    beyond the convs' BatchNorm column sums, fp32 fc."""
+    dev = x.device
+    N, _, H, W = x.shape
+    f32 = torch.float32
+    specs = resnet18_convs(in_ch)
+    mirrors = weight_mirrors(P, specs, False, f32)
+    stats = torch.zeros(2 * ops.CONV_STAT_REPS * sum(sp.cout for sp in specs), device=dev,
+                        dtype=torch.int64) if training else None
+    st = ResNetSaved(N, mirrors=mirrors)
+    sp = specs[0]
+    x0 = torch.empty(N, H, W, STEM_CP, device=dev, dtype=f32)
+    ops.nchw_to_nhwc(x.contiguous().float(), STEM_CP, x0)
+    act = _conv_bn(P, bufs, sp, x0, N, H, W, mirrors, stats, 0, None, True, training)
+    st.acts[sp.name] = act
+    Hc, Wc = act.y.shape[1], act.y.shape[2]
+    Hp, Wp = ops.conv_out_hw(Hc, Wc, 3, 2, 1)
+    y = torch.empty(N, Hp, Wp, sp.cout, device=dev, dtype=f32)
+    st.pool_idx = torch.empty(N, Hp, Wp, sp.cout, device=dev, dtype=torch.uint8)
+    ops.maxpool_fwd(act.a, 3, 2, 1, y, st.pool_idx)
+    y = _res_stages_fwd(P, bufs, specs, st, y, N, Hp, Wp, mirrors, stats,
+                        2 * ops.CONV_STAT_REPS * sp.cout, training)
+    st.feat = ops.avgpool_fwd(y, torch.empty(N, 512, device=dev, dtype=f32))
+    st.fc_w = P["fc.weight"].contiguous()
+    out = torch.empty(N, st.fc_w.shape[0], device=dev)
+    ops.linear(st.feat, st.fc_w, P["fc.bias"], out)
     return out, st
 
 
 def resnet18_bwd(P: Dict[str, Tensor], st: ResNetSaved, dout: Tensor, grads: Dict[str, Tensor],
                  in_ch: int) -> None:
-    """Backward of resnet18_fwd: accumulates every parameter grad (torch layouts)."""
+    """Backward of resnet18_fwd: accumulates every parameter grad (torch layouts).  Follows the
+    saved state's storage dtype: an fp32 state takes the unfused path (every BatchNorm backward
+    as reduce + apply of its own, maxpool_bwd → bn2d_bwd for the stem)."""
     dev = dout.device
+    fused = st.last.dtype == torch.bfloat16    # DGRAD-fused BN reductions, fused stem pool
     N = st.N
     specs = resnet18_convs(in_ch)
     byname = {s.name: s for s in specs}
@@ -255,7 +322,7 @@ def resnet18_bwd(P: Dict[str, Tensor], st: ResNetSaved, dout: Tensor, grads: Dic
             return None
         dx = torch.empty_like(act.x)
         bn = None
-        if bn_of is not None:
+        if bn_of is not None and fused:
             bsp, bact = bn_of
             bn = (bact.a, bact.y, bact.mean, bact.rstd, sl[bsp.name])
         ops.conv2d(ops.DGRAD, N, act.H, act.W, C, sp.cin, sp.cout, sp.k, sp.stride, sp.pad,
@@ -287,7 +354,7 @@ def resnet18_bwd(P: Dict[str, Tensor], st: ResNetSaved, dout: Tensor, grads: Dic
             g = torch.empty_like(a2.a)
             d2 = bn_bwd(c2, a2, dy, a2.a, g_out=g)
         g1 = conv_bwd(c2, a2, d2, True, bn_of=(c1, a1))
-        d1 = bn_apply(c1, a1, g1)
+        d1 = bn_apply(c1, a1, g1) if fused else bn_bwd(c1, a1, g1, a1.a)
         if ds is not None:
             ad = st.acts[ds.name]
             dd = bn_bwd(ds, ad, g, None)
@@ -299,14 +366,18 @@ def resnet18_bwd(P: Dict[str, Tensor], st: ResNetSaved, dout: Tensor, grads: Dic
             pc2 = byname[fwd_blocks[j - 1] + "conv2.weight"]
             prev = (pc2, st.acts[pc2.name])
         dy = conv_bwd(c1, a1, d1, True, addend=idn_dx, bn_of=prev)
-        gated = prev is not None
+        gated = fused and prev is not None
     # max-pool and stem (no input grad: the encoder input is data)
     stem = specs[0]
     act = st.acts[stem.name]
-    d0 = torch.empty_like(act.y)
-    ops.stem_pool_bwd(dy, st.pool_idx, act.y, act.mean, act.rstd, P[stem.bn + ".weight"],
-                      P[stem.bn + ".bias"], sl[stem.name], d0, grads[stem.bn + ".weight"],
-                      grads[stem.bn + ".bias"])
+    if fused:
+        d0 = torch.empty_like(act.y)
+        ops.stem_pool_bwd(dy, st.pool_idx, act.y, act.mean, act.rstd, P[stem.bn + ".weight"],
+                          P[stem.bn + ".bias"], sl[stem.name], d0, grads[stem.bn + ".weight"],
+                          grads[stem.bn + ".bias"])
+    else:
+        da = ops.maxpool_bwd(dy, st.pool_idx, 3, 2, 1, torch.empty_like(act.a))
+        d0 = bn_bwd(stem, act, da, act.a)
     conv_bwd(stem, act, d0, False)
 
 
@@ -323,10 +394,19 @@ class TabSaved:
     p_drop: float
 
 
+def _operand(src: Tensor, dtype: torch.dtype) -> Tensor:
+    """A GEMM operand of ``src`` (fp32) in ``dtype``: the bf16 cast, or src itself for fp32."""
+    if dtype == torch.float32:
+        return src
+    return ops.cast_bf16(src, torch.empty(src.shape, device=src.device, dtype=dtype))
+
+
 def tabular_fwd(P: Dict[str, Tensor], x: Tensor, bufs: Dict[str, Tensor], seeds: Optional[Tensor],
                 p_drop: float, site: int = F.SITE_TAB, training: bool = True,
                 dtype=torch.bfloat16):
-    """TabularEncoder (item_tower.py:85-98): Linear → BN1d → ReLU → Dropout → Linear."""
+    """TabularEncoder (item_tower.py:85-98): Linear → BN1d → ReLU → Dropout → Linear.  dtype:
+    the GEMM operand storage (bf16, or fp32 for the reference-parity mode)."""
+    check_dtype(dtype, "tabular_fwd")
     dev = x.device
     B, T = x.shape
     if T % 8:
@@ -339,11 +419,9 @@ def tabular_fwd(P: Dict[str, Tensor], x: Tensor, bufs: Dict[str, Tensor], seeds:
                             torch.zeros(P["mlp.0.weight"].shape[0], Tp, device=dev, dtype=dtype)[:, :T])
         w0 = w0.as_strided((w0.shape[0], Tp), (Tp, 1))
     else:
-        xc = ops.cast_bf16(x.contiguous().float(), torch.empty(x.shape, device=dev, dtype=dtype))
-        w0 = ops.cast_bf16(P["mlp.0.weight"].contiguous(),
-                           torch.empty(P["mlp.0.weight"].shape, device=dev, dtype=dtype))
-    w4 = ops.cast_bf16(P["mlp.4.weight"].contiguous(),
-                       torch.empty(P["mlp.4.weight"].shape, device=dev, dtype=dtype))
+        xc = _operand(x.contiguous().float(), dtype)
+        w0 = _operand(P["mlp.0.weight"].contiguous(), dtype)
+    w4 = _operand(P["mlp.4.weight"].contiguous(), dtype)
     H1 = w0.shape[0]
     z = torch.empty(B, H1, device=dev)
     ops.linear(xc, w0, P["mlp.0.bias"], z)
@@ -403,9 +481,9 @@ class BasicBlock(nn.Module):
 
 class _ResNetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, in_ch, names, bufs, x, *params):
+    def forward(ctx, in_ch, names, bufs, dtype, x, *params):
         P = dict(zip(names, params))
-        out, st = resnet18_fwd(P, x, in_ch, bufs, training=True)
+        out, st = resnet18_fwd(P, x, in_ch, bufs, training=True, dtype=dtype)
         ctx.saved = (in_ch, names, P, st)
         return out
 
@@ -415,15 +493,18 @@ class _ResNetFn(torch.autograd.Function):
         del ctx.saved
         grads = {n: torch.zeros_like(P[n]) for n in names}
         resnet18_bwd(P, st, dout, grads, in_ch)
-        return (None, None, None, None) + tuple(grads[n] for n in names)
+        return (None, None, None, None, None) + tuple(grads[n] for n in names)
 
 
 class ResNet18(nn.Module):
     """torchvision resnet18 with conv1 → Conv2d(in_ch, 64, 7, 2, 3) and fc → Linear(512, out_dim)
-    (AudioEncoder/VisualEncoder backbones, item_tower.py:15-22, :33-36)."""
+    (AudioEncoder/VisualEncoder backbones, item_tower.py:15-22, :33-36).  ``dtype``: activation
+    storage, torch.bfloat16 or torch.float32 (module docstring); parameters and state_dict do
+    not depend on it."""
 
-    def __init__(self, in_ch: int = 3, out_dim: int = 128):
+    def __init__(self, in_ch: int = 3, out_dim: int = 128, dtype: torch.dtype = torch.bfloat16):
         super().__init__()
+        self.dtype = check_dtype(dtype, "ResNet18")
         self.in_ch = in_ch
         self.conv1 = nn.Conv2d(in_ch, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -441,18 +522,18 @@ class ResNet18(nn.Module):
         names, params = zip(*self.named_parameters())
         bufs = dict(self.named_buffers())
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _ResNetFn.apply(self.in_ch, list(names), bufs, x, *params)
+            return _ResNetFn.apply(self.in_ch, list(names), bufs, self.dtype, x, *params)
         out, _ = resnet18_fwd(dict(zip(names, [p.detach() for p in params])), x, self.in_ch,
-                              bufs, training=self.training)
+                              bufs, training=self.training, dtype=self.dtype)
         return out
 
 
 class AudioEncoder(nn.Module):
     """item_tower.py:9-25: ResNet-18 on 1-channel mel spectrograms, fc → embedding_dim."""
 
-    def __init__(self, embedding_dim: int = 128):
+    def __init__(self, embedding_dim: int = 128, dtype: torch.dtype = torch.bfloat16):
         super().__init__()
-        self.backbone = ResNet18(1, embedding_dim)
+        self.backbone = ResNet18(1, embedding_dim, dtype=dtype)
 
     def forward(self, x: Tensor) -> Tensor:
         return self.backbone(x)
@@ -462,9 +543,10 @@ class VisualEncoder(nn.Module):
     """item_tower.py:27-39: ResNet-18 on 3-channel covers (ImageNet weights are a download and
     are not available offline: random init), fc → embedding_dim."""
 
-    def __init__(self, embedding_dim: int = 128, pretrained: bool = False):
+    def __init__(self, embedding_dim: int = 128, pretrained: bool = False,
+                 dtype: torch.dtype = torch.bfloat16):
         super().__init__()
-        self.backbone = ResNet18(3, embedding_dim)
+        self.backbone = ResNet18(3, embedding_dim, dtype=dtype)
 
     def forward(self, x: Tensor) -> Tensor:
         return self.backbone(x)
@@ -472,9 +554,9 @@ class VisualEncoder(nn.Module):
 
 class _TabularFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, names, bufs, p_drop, seeds, x, *params):
+    def forward(ctx, names, bufs, p_drop, seeds, dtype, x, *params):
         P = dict(zip(names, params))
-        out, st = tabular_fwd(P, x, bufs, seeds, p_drop)
+        out, st = tabular_fwd(P, x, bufs, seeds, p_drop, dtype=dtype)
         ctx.saved = (names, P, st)
         return out
 
@@ -484,14 +566,15 @@ class _TabularFn(torch.autograd.Function):
         del ctx.saved
         grads = {n: torch.zeros_like(P[n]) for n in names}
         tabular_bwd(P, st, dout, grads)
-        return (None, None, None, None, None) + tuple(grads[n] for n in names)
+        return (None, None, None, None, None, None) + tuple(grads[n] for n in names)
 
 
 class TabularEncoder(nn.Module):
-    """item_tower.py:85-98."""
+    """item_tower.py:85-98.  ``dtype``: GEMM operand storage, torch.bfloat16 or torch.float32."""
 
-    def __init__(self, input_dim: int, embedding_dim: int = 128):
+    def __init__(self, input_dim: int, embedding_dim: int = 128, dtype: torch.dtype = torch.bfloat16):
         super().__init__()
+        self.dtype = check_dtype(dtype, "TabularEncoder")
         self.mlp = nn.Sequential(nn.Linear(input_dim, 256), nn.BatchNorm1d(256), nn.ReLU(),
                                  nn.Dropout(0.1), nn.Linear(256, embedding_dim))
 
@@ -503,7 +586,7 @@ class TabularEncoder(nn.Module):
             seeds = torch.randint(-(2 ** 62), 2 ** 62, (F.N_SITES,), device=x.device,
                                   dtype=torch.int64)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _TabularFn.apply(list(names), bufs, p_drop, seeds, x, *params)
+            return _TabularFn.apply(list(names), bufs, p_drop, seeds, self.dtype, x, *params)
         out, _ = tabular_fwd(dict(zip(names, [p.detach() for p in params])), x, bufs, seeds,
-                             p_drop, training=self.training)
+                             p_drop, training=self.training, dtype=self.dtype)
         return out

@@ -12,6 +12,8 @@
 // writing g for the residual branch) and an element-wise pass
 //   dx = w·rstd·(g − Σg/M − x̂·Σg x̂/M).
 // Element-wise passes move 8 channels (16 bytes) per thread.
+// Every kernel but the fused stem pool is written over the storage type (V8<T> below): bf16,
+// or fp32 for the reference-parity mode (the ttmi_*_f32 entry points; 8 channels = 32 bytes).
 #include "ttmi_common.h"
 
 namespace {
@@ -22,16 +24,45 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n 
 constexpr int EW_U = 4;     // 16-byte items per thread per trip in the element-wise BN passes
 int grid_ew(int64_t n) { return grid_for((n + EW_U - 1) / EW_U); }
 
+// 8 consecutive channels of an activation, indexed in units of 8 elements: one 16-byte chunk
+// in bf16 storage, two in fp32 storage (the reference-parity mode, ttmi_*_f32).  The kernels
+// below are written once over the storage type T; all arithmetic is fp32 either way.
+template <typename T> struct V8;
+template <> struct V8<bf16_t> {
+  uint4 q;
+  static TTMI_DEV V8 ld(const bf16_t* p, int64_t i) { return V8{reinterpret_cast<const uint4*>(p)[i]}; }
+  static TTMI_DEV V8 zero() { return V8{make_uint4(0u, 0u, 0u, 0u)}; }
+  TTMI_DEV void get(float* v) const { unpack8(q, v); }
+  static TTMI_DEV void st(bf16_t* p, int64_t i, const float* v) { reinterpret_cast<uint4*>(p)[i] = pack8(v); }
+};
+template <> struct V8<float> {
+  float4 a, b;
+  static TTMI_DEV V8 ld(const float* p, int64_t i) {
+    const float4* q = reinterpret_cast<const float4*>(p) + 2 * i;
+    return V8{q[0], q[1]};
+  }
+  static TTMI_DEV V8 zero() { return V8{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)}; }
+  TTMI_DEV void get(float* v) const {
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  static TTMI_DEV void st(float* p, int64_t i, const float* v) {
+    float4* q = reinterpret_cast<float4*>(p) + 2 * i;
+    q[0] = make_float4(v[0], v[1], v[2], v[3]);
+    q[1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+};
+
 // ---------------------------------------------------------------- BatchNorm2d forward
-__global__ __launch_bounds__(256) void bn2d_fwd_kernel(int64_t M, int C, const bf16_t* __restrict__ x,
+template <typename T>
+__global__ __launch_bounds__(256) void bn2d_fwd_kernel(int64_t M, int C, const T* __restrict__ x,
                                                        const int64_t* __restrict__ csum,
                                                        const int64_t* __restrict__ csq,
                                                        const float* __restrict__ w,
                                                        const float* __restrict__ b, float eps,
                                                        float momentum, float* running_mean,
                                                        float* running_var, int64_t* nbt,
-                                                       const bf16_t* __restrict__ res, int relu,
-                                                       bf16_t* __restrict__ y, float* save_mean,
+                                                       const T* __restrict__ res, int relu,
+                                                       T* __restrict__ y, float* save_mean,
                                                        float* save_rstd) {
   __shared__ float sa[MAXC], sb[MAXC];      // y = x·sa + sb
   const bool eval = csum == nullptr;        // eval mode: normalise with the running statistics
@@ -68,12 +99,12 @@ __global__ __launch_bounds__(256) void bn2d_fwd_kernel(int64_t M, int C, const b
   // trip left the pass latency-bound at ~half the HBM rate)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x * EW_U;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x * EW_U + threadIdx.x; i0 < n; i0 += stride) {
-    uint4 qx[EW_U], qr[EW_U];
+    V8<T> qx[EW_U], qr[EW_U];
 #pragma unroll
     for (int u = 0; u < EW_U; ++u) {
       const int64_t i = min(i0 + (int64_t)u * blockDim.x, n - 1);
-      qx[u] = reinterpret_cast<const uint4*>(x)[i];
-      qr[u] = res ? reinterpret_cast<const uint4*>(res)[i] : make_uint4(0u, 0u, 0u, 0u);
+      qx[u] = V8<T>::ld(x, i);
+      qr[u] = res ? V8<T>::ld(res, i) : V8<T>::zero();
     }
 #pragma unroll
     for (int u = 0; u < EW_U; ++u) {
@@ -81,14 +112,14 @@ __global__ __launch_bounds__(256) void bn2d_fwd_kernel(int64_t M, int C, const b
       if (i >= n) break;
       const int c0 = (int)(i % cpr) * 8;
       float v[8], r[8];
-      unpack8(qx[u], v);
-      unpack8(qr[u], r);
+      qx[u].get(v);
+      qr[u].get(r);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         v[e] = v[e] * sa[c0 + e] + sb[c0 + e] + r[e];
         if (relu) v[e] = fmaxf(v[e], 0.f);
       }
-      reinterpret_cast<uint4*>(y)[i] = pack8(v);
+      V8<T>::st(y, i, v);
     }
   }
 }
@@ -99,12 +130,13 @@ __global__ __launch_bounds__(256) void bn2d_fwd_kernel(int64_t M, int C, const b
 // 256 threads over row slabs; per thread 8 channels of strided rows, then an LDS reduction (a
 // fixed order) and one int64 fixed-point add (TTMI_FX_GRAD) per channel per block into its
 // replica row (spread: no single hot address; order-independent: deterministic).
-__global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(int64_t M, int C, const bf16_t* __restrict__ dy,
-                                                              const bf16_t* __restrict__ gate,
-                                                              const bf16_t* __restrict__ x,
+template <typename T>
+__global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(int64_t M, int C, const T* __restrict__ dy,
+                                                              const T* __restrict__ gate,
+                                                              const T* __restrict__ x,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ rstd,
-                                                              bf16_t* __restrict__ gout,
+                                                              T* __restrict__ gout,
                                                               int64_t* __restrict__ sums,
                                                               int64_t rows_per_block) {
   __shared__ float red[2][256][8];
@@ -123,13 +155,13 @@ __global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(int64_t M, int C, 
     // ~25 rows: one dependent memory latency per row made this a latency chain)
     constexpr int U = 4;
     for (int64_t mb = r0 + rl; mb < r1; mb += U * tpr) {
-      uint4 qd[U], qg[U], qx[U];
+      V8<T> qd[U], qg[U], qx[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t i = min(mb + u * tpr, r1 - 1) * cpr + cg;
-        qd[u] = reinterpret_cast<const uint4*>(dy)[i];
-        qg[u] = gate ? reinterpret_cast<const uint4*>(gate)[i] : make_uint4(0u, 0u, 0u, 0u);
-        qx[u] = reinterpret_cast<const uint4*>(x)[i];
+        qd[u] = V8<T>::ld(dy, i);
+        qg[u] = gate ? V8<T>::ld(gate, i) : V8<T>::zero();
+        qx[u] = V8<T>::ld(x, i);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -137,15 +169,15 @@ __global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(int64_t M, int C, 
         if (m >= r1) break;
         const int64_t i = m * cpr + cg;
         float g[8], xv[8];
-        unpack8(qd[u], g);
+        qd[u].get(g);
         if (gate) {
           float gv[8];
-          unpack8(qg[u], gv);
+          qg[u].get(gv);
 #pragma unroll
           for (int e = 0; e < 8; ++e) g[e] = gv[e] > 0.f ? g[e] : 0.f;
         }
-        if (gout) reinterpret_cast<uint4*>(gout)[i] = pack8(g);
-        unpack8(qx[u], xv);
+        if (gout) V8<T>::st(gout, i, g);
+        qx[u].get(xv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           s1[e] += g[e];
@@ -173,14 +205,15 @@ __global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(int64_t M, int C, 
 }
 
 // dx = w·rstd·(g − Σg/M − x̂·Σgx̂/M) (+ addend); block 0 also adds the sums into dw/db.
-__global__ __launch_bounds__(256) void bn2d_bwd_apply_kernel(int64_t M, int C, const bf16_t* __restrict__ dy,
-                                                             const bf16_t* __restrict__ gate,
-                                                             const bf16_t* __restrict__ x,
+template <typename T>
+__global__ __launch_bounds__(256) void bn2d_bwd_apply_kernel(int64_t M, int C, const T* __restrict__ dy,
+                                                             const T* __restrict__ gate,
+                                                             const T* __restrict__ x,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
                                                              const float* __restrict__ w,
                                                              const int64_t* __restrict__ sums,
-                                                             bf16_t* __restrict__ dx,
+                                                             T* __restrict__ dx,
                                                              float* dw, float* db) {
   __shared__ float sk[MAXC], sm1[MAXC], sm2[MAXC], smu[MAXC], srs[MAXC];
   const float invM = 1.f / (float)M;
@@ -206,13 +239,13 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply_kernel(int64_t M, int C, c
   const int64_t n = M * cpr;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x * EW_U;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x * EW_U + threadIdx.x; i0 < n; i0 += stride) {
-    uint4 qd[EW_U], qg[EW_U], qx[EW_U];
+    V8<T> qd[EW_U], qg[EW_U], qx[EW_U];
 #pragma unroll
     for (int u = 0; u < EW_U; ++u) {
       const int64_t i = min(i0 + (int64_t)u * blockDim.x, n - 1);
-      qd[u] = reinterpret_cast<const uint4*>(dy)[i];
-      qg[u] = gate ? reinterpret_cast<const uint4*>(gate)[i] : make_uint4(0u, 0u, 0u, 0u);
-      qx[u] = reinterpret_cast<const uint4*>(x)[i];
+      qd[u] = V8<T>::ld(dy, i);
+      qg[u] = gate ? V8<T>::ld(gate, i) : V8<T>::zero();
+      qx[u] = V8<T>::ld(x, i);
     }
 #pragma unroll
     for (int u = 0; u < EW_U; ++u) {
@@ -220,30 +253,31 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply_kernel(int64_t M, int C, c
       if (i >= n) break;
       const int c0 = (int)(i % cpr) * 8;
       float g[8], xv[8], o[8];
-      unpack8(qd[u], g);
+      qd[u].get(g);
       if (gate) {
         float gv[8];
-        unpack8(qg[u], gv);
+        qg[u].get(gv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g[e] = gv[e] > 0.f ? g[e] : 0.f;
       }
-      unpack8(qx[u], xv);
+      qx[u].get(xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int c = c0 + e;
         const float xh = (xv[e] - smu[c]) * srs[c];
         o[e] = sk[c] * (g[e] - sm1[c] - xh * sm2[c]);
       }
-      reinterpret_cast<uint4*>(dx)[i] = pack8(o);
+      V8<T>::st(dx, i, o);
     }
   }
 }
 
 // ---------------------------------------------------------------- pools
 // max-pool k x k / s, padding p (-inf), NHWC; idx = window tap of the max (first on ties).
+template <typename T>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int N, int H, int W, int C, int Ho, int Wo, int k,
-                                                          int s, int p, const bf16_t* __restrict__ x,
-                                                          bf16_t* __restrict__ y, uint8_t* __restrict__ idx) {
+                                                          int s, int p, const T* __restrict__ x,
+                                                          T* __restrict__ y, uint8_t* __restrict__ idx) {
   const int cpr = C / 8;
   const int n = N * Ho * Wo * cpr;                    // < 2^31 (host-checked): 32-bit math
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -263,13 +297,13 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int N, int H, int W, i
         const int w = wo * s - p + kw;
         if (w < 0 || w >= W) continue;
         float v[8];
-        unpack8(*reinterpret_cast<const uint4*>(x + (((int64_t)b * H + h) * W + w) * C + cg * 8), v);
+        V8<T>::ld(x, (((int64_t)b * H + h) * W + w) * cpr + cg).get(v);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           if (v[e] > best[e]) { best[e] = v[e]; arg[e] = (uint8_t)(kh * k + kw); }
       }
     }
-    reinterpret_cast<uint4*>(y)[i] = pack8(best);
+    V8<T>::st(y, i, best);
     uint2 a;
     a.x = (uint32_t)arg[0] | ((uint32_t)arg[1] << 8) | ((uint32_t)arg[2] << 16) | ((uint32_t)arg[3] << 24);
     a.y = (uint32_t)arg[4] | ((uint32_t)arg[5] << 8) | ((uint32_t)arg[6] << 16) | ((uint32_t)arg[7] << 24);
@@ -278,10 +312,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int N, int H, int W, i
 }
 
 // dx[h, w] = Σ over the windows that chose (h, w) of dy (gather form: deterministic).
+template <typename T>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(int N, int H, int W, int C, int Ho, int Wo, int k,
-                                                          int s, int p, const bf16_t* __restrict__ dy,
+                                                          int s, int p, const T* __restrict__ dy,
                                                           const uint8_t* __restrict__ idx,
-                                                          bf16_t* __restrict__ dx) {
+                                                          T* __restrict__ dx) {
   const int cpr = C / 8;
   const int n = N * H * W * cpr;                      // < 2^31 (host-checked): 32-bit math
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -303,7 +338,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(int N, int H, int W, i
         const int64_t o = ((((int64_t)b * Ho + ho) * Wo + wo) * cpr + cg);
         const uint2 a = reinterpret_cast<const uint2*>(idx)[o];
         float g[8];
-        unpack8(reinterpret_cast<const uint4*>(dy)[o], g);
+        V8<T>::ld(dy, o).get(g);
         const uint8_t tap = (uint8_t)(kh * k + kw);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -312,40 +347,42 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(int N, int H, int W, i
         }
       }
     }
-    reinterpret_cast<uint4*>(dx)[i] = pack8(acc);
+    V8<T>::st(dx, i, acc);
   }
 }
 
 // y[n, c] = mean over H·W of x[n, :, :, c] (fp32 accumulate; out bf16).  Block per (n, 64-ch).
-__global__ __launch_bounds__(256) void avgpool_fwd_kernel(int N, int HW, int C, const bf16_t* __restrict__ x,
-                                                          bf16_t* __restrict__ y) {
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool_fwd_kernel(int N, int HW, int C, const T* __restrict__ x,
+                                                          T* __restrict__ y) {
   __shared__ float red[4][64];
   const int b = blockIdx.x / ((C + 63) / 64), c = (blockIdx.x % ((C + 63) / 64)) * 64 + (threadIdx.x & 63);
   const int rl = threadIdx.x >> 6;
   float s = 0.f;
   if (c < C)
-    for (int p = rl; p < HW; p += 4) s += bf2f(x[((int64_t)b * HW + p) * C + c]);
+    for (int p = rl; p < HW; p += 4) s += ldf(x, ((int64_t)b * HW + p) * C + c);
   red[rl][threadIdx.x & 63] = s;
   __syncthreads();
   if (rl == 0 && c < C) {
     const float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-    y[(int64_t)b * C + c] = f2bf(t / (float)HW);
+    stf(y, (int64_t)b * C + c, t / (float)HW);
   }
 }
 
 // dx[n, p, c] = dy[n, c] / HW (dy fp32 or bf16), optionally gated by (gate > 0): the ReLU at
 // the end of the last block.
+template <typename T>
 __global__ __launch_bounds__(256) void avgpool_bwd_kernel(int N, int HW, int C, const void* __restrict__ dy,
-                                                          int dy_f32, const bf16_t* __restrict__ gate,
-                                                          bf16_t* __restrict__ dx) {
+                                                          int dy_f32, const T* __restrict__ gate,
+                                                          T* __restrict__ dx) {
   const int64_t n = (int64_t)N * HW * C;
   const float inv = 1.f / (float)HW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const int b = (int)(i / ((int64_t)HW * C));
     float g = ld_dyn(dy, (int64_t)b * C + c, dy_f32) * inv;
-    if (gate && bf2f(gate[i]) <= 0.f) g = 0.f;
-    dx[i] = f2bf(g);
+    if (gate && ldf(gate, i) <= 0.f) g = 0.f;
+    stf(dx, i, g);
   }
 }
 
@@ -794,49 +831,137 @@ __global__ __launch_bounds__(256) void stem_quad_bwd_apply_kernel(int N, int H, 
 
 }  // namespace
 
-extern "C" int ttmi_bn2d_fwd(int64_t M, int C, const uint16_t* x, const int64_t* colsum,
-                             const int64_t* colsumsq, const float* w, const float* b, float eps,
-                             float momentum, float* running_mean, float* running_var,
-                             int64_t* num_batches_tracked, const uint16_t* residual, int relu,
-                             uint16_t* y, float* save_mean, float* save_rstd, hipStream_t s) {
-  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "ttmi_bn2d_fwd: need 0 < C <= %d, C %% 8 == 0", MAXC);
-  TTMI_REQUIRE(x && w && b && y && save_mean && save_rstd, "ttmi_bn2d_fwd: null argument");
-  TTMI_REQUIRE(!running_mean == !running_var, "ttmi_bn2d_fwd: running_mean/var go together");
-  TTMI_REQUIRE(!colsum == !colsumsq, "ttmi_bn2d_fwd: colsum/colsumsq go together");
-  TTMI_REQUIRE(colsum || running_mean, "ttmi_bn2d_fwd: eval mode (no colsum) needs running stats");
-  hipLaunchKernelGGL(bn2d_fwd_kernel, dim3(grid_ew(M * C / 8)), dim3(256), 0, s, M, C, (const bf16_t*)x,
-                     colsum, colsumsq, w, b, eps, momentum, running_mean, running_var,
-                     num_batches_tracked, (const bf16_t*)residual, relu, (bf16_t*)y, save_mean, save_rstd);
-  return ttmi_check_launch("ttmi_bn2d_fwd");
+namespace {
+
+template <typename T>
+int bn2d_fwd_t(const char* who, int64_t M, int C, const T* x, const int64_t* colsum, const int64_t* colsumsq,
+               const float* w, const float* b, float eps, float momentum, float* running_mean,
+               float* running_var, int64_t* num_batches_tracked, const T* residual, int relu, T* y,
+               float* save_mean, float* save_rstd, hipStream_t s) {
+  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "%s: need 0 < C <= %d, C %% 8 == 0", who, MAXC);
+  TTMI_REQUIRE(x && w && b && y && save_mean && save_rstd, "%s: null argument", who);
+  TTMI_REQUIRE(!running_mean == !running_var, "%s: running_mean/var go together", who);
+  TTMI_REQUIRE(!colsum == !colsumsq, "%s: colsum/colsumsq go together", who);
+  TTMI_REQUIRE(colsum || running_mean, "%s: eval mode (no colsum) needs running stats", who);
+  hipLaunchKernelGGL(bn2d_fwd_kernel<T>, dim3(grid_ew(M * C / 8)), dim3(256), 0, s, M, C, x, colsum, colsumsq, w,
+                     b, eps, momentum, running_mean, running_var, num_batches_tracked, residual, relu, y,
+                     save_mean, save_rstd);
+  return ttmi_check_launch(who);
 }
 
-extern "C" int ttmi_bn2d_bwd_reduce(int64_t M, int C, const uint16_t* dy, const uint16_t* gate,
-                                    const uint16_t* x, const float* mean, const float* rstd, int64_t* sums,
-                                    uint16_t* g_out, hipStream_t s) {
-  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "ttmi_bn2d_bwd_reduce: need 0 < C <= %d, C %% 8 == 0",
-               MAXC);
-  TTMI_REQUIRE(dy && x && mean && rstd && sums, "ttmi_bn2d_bwd_reduce: null argument");
+template <typename T>
+int bn2d_bwd_reduce_t(const char* who, int64_t M, int C, const T* dy, const T* gate, const T* x, const float* mean,
+                      const float* rstd, int64_t* sums, T* g_out, hipStream_t s) {
+  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "%s: need 0 < C <= %d, C %% 8 == 0", who, MAXC);
+  TTMI_REQUIRE(dy && x && mean && rstd && sums, "%s: null argument", who);
   const int cpr = C / 8;
   const int tpr = std::max(1, 256 / cpr);
   int64_t blocks = std::min<int64_t>(1024, (M + tpr * 8 - 1) / (tpr * 8));
   blocks = std::max<int64_t>(blocks, 1);
   const int64_t rpb = (M + blocks - 1) / blocks;
-  hipLaunchKernelGGL(bn2d_bwd_reduce_kernel, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, s, M, C,
-                     (const bf16_t*)dy, (const bf16_t*)gate, (const bf16_t*)x, mean, rstd, (bf16_t*)g_out,
-                     sums, rpb);
-  return ttmi_check_launch("ttmi_bn2d_bwd_reduce");
+  hipLaunchKernelGGL(bn2d_bwd_reduce_kernel<T>, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, s, M, C, dy,
+                     gate, x, mean, rstd, g_out, sums, rpb);
+  return ttmi_check_launch(who);
+}
+
+template <typename T>
+int bn2d_bwd_apply_t(const char* who, int64_t M, int C, const T* dy, const T* gate, const T* x, const float* mean,
+                     const float* rstd, const float* w, const int64_t* sums, T* dx, float* dw, float* db,
+                     hipStream_t s) {
+  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "%s: need 0 < C <= %d, C %% 8 == 0", who, MAXC);
+  TTMI_REQUIRE(dy && x && mean && rstd && w && sums && dx, "%s: null argument", who);
+  hipLaunchKernelGGL(bn2d_bwd_apply_kernel<T>, dim3(grid_ew(M * C / 8)), dim3(256), 0, s, M, C, dy, gate, x, mean,
+                     rstd, w, sums, dx, dw, db);
+  return ttmi_check_launch(who);
+}
+
+template <typename T>
+int maxpool_fwd_t(const char* who, int N, int H, int W, int C, int k, int stride, int pad, const T* x, T* y,
+                  uint8_t* idx, hipStream_t s) {
+  TTMI_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && k > 0 && k * k <= 255 && stride > 0 &&
+                   pad >= 0 && pad < k, "%s: bad shape", who);
+  TTMI_REQUIRE(x && y && idx, "%s: null argument", who);
+  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  if (N == 0) return TTMI_OK;
+  TTMI_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "%s: tensor too large", who);
+  hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid_for((int64_t)N * Ho * Wo * C / 8)), dim3(256), 0, s, N, H,
+                     W, C, Ho, Wo, k, stride, pad, x, y, idx);
+  return ttmi_check_launch(who);
+}
+
+template <typename T>
+int maxpool_bwd_t(const char* who, int N, int H, int W, int C, int k, int stride, int pad, const T* dy,
+                  const uint8_t* idx, T* dx, hipStream_t s) {
+  TTMI_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && k > 0 && stride > 0 && pad >= 0,
+               "%s: bad shape", who);
+  TTMI_REQUIRE(dy && idx && dx, "%s: null argument", who);
+  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  if (N == 0) return TTMI_OK;
+  TTMI_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "%s: tensor too large", who);
+  hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(grid_for((int64_t)N * H * W * C / 8)), dim3(256), 0, s, N, H, W,
+                     C, Ho, Wo, k, stride, pad, dy, idx, dx);
+  return ttmi_check_launch(who);
+}
+
+template <typename T>
+int avgpool_fwd_t(const char* who, int N, int HW, int C, const T* x, T* y, hipStream_t s) {
+  TTMI_REQUIRE(N >= 0 && HW > 0 && C > 0, "%s: bad shape", who);
+  TTMI_REQUIRE(x && y, "%s: null argument", who);
+  if (N == 0) return TTMI_OK;
+  hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(N * ((C + 63) / 64)), dim3(256), 0, s, N, HW, C, x, y);
+  return ttmi_check_launch(who);
+}
+
+template <typename T>
+int avgpool_bwd_t(const char* who, int N, int HW, int C, const void* dy, int dy_dtype, const T* gate, T* dx,
+                  hipStream_t s) {
+  TTMI_REQUIRE(N >= 0 && HW > 0 && C > 0, "%s: bad shape", who);
+  TTMI_REQUIRE(dy && dx, "%s: null argument", who);
+  if (N == 0) return TTMI_OK;
+  hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(grid_for((int64_t)N * HW * C)), dim3(256), 0, s, N, HW, C, dy,
+                     dy_dtype == TTMI_F32, gate, dx);
+  return ttmi_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int ttmi_bn2d_fwd(int64_t M, int C, const uint16_t* x, const int64_t* colsum,
+                             const int64_t* colsumsq, const float* w, const float* b, float eps,
+                             float momentum, float* running_mean, float* running_var,
+                             int64_t* num_batches_tracked, const uint16_t* residual, int relu,
+                             uint16_t* y, float* save_mean, float* save_rstd, hipStream_t s) {
+  return bn2d_fwd_t<bf16_t>("ttmi_bn2d_fwd", M, C, x, colsum, colsumsq, w, b, eps, momentum, running_mean,
+                            running_var, num_batches_tracked, residual, relu, y, save_mean, save_rstd, s);
+}
+extern "C" int ttmi_bn2d_fwd_f32(int64_t M, int C, const float* x, const int64_t* colsum,
+                                 const int64_t* colsumsq, const float* w, const float* b, float eps,
+                                 float momentum, float* running_mean, float* running_var,
+                                 int64_t* num_batches_tracked, const float* residual, int relu, float* y,
+                                 float* save_mean, float* save_rstd, hipStream_t s) {
+  return bn2d_fwd_t<float>("ttmi_bn2d_fwd_f32", M, C, x, colsum, colsumsq, w, b, eps, momentum, running_mean,
+                           running_var, num_batches_tracked, residual, relu, y, save_mean, save_rstd, s);
+}
+
+extern "C" int ttmi_bn2d_bwd_reduce(int64_t M, int C, const uint16_t* dy, const uint16_t* gate,
+                                    const uint16_t* x, const float* mean, const float* rstd, int64_t* sums,
+                                    uint16_t* g_out, hipStream_t s) {
+  return bn2d_bwd_reduce_t<bf16_t>("ttmi_bn2d_bwd_reduce", M, C, dy, gate, x, mean, rstd, sums, g_out, s);
+}
+extern "C" int ttmi_bn2d_bwd_reduce_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                                        const float* mean, const float* rstd, int64_t* sums, float* g_out,
+                                        hipStream_t s) {
+  return bn2d_bwd_reduce_t<float>("ttmi_bn2d_bwd_reduce_f32", M, C, dy, gate, x, mean, rstd, sums, g_out, s);
 }
 
 extern "C" int ttmi_bn2d_bwd_apply(int64_t M, int C, const uint16_t* dy, const uint16_t* gate,
                                    const uint16_t* x, const float* mean, const float* rstd, const float* w,
                                    const int64_t* sums, uint16_t* dx, float* dw, float* db, hipStream_t s) {
-  TTMI_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= MAXC, "ttmi_bn2d_bwd_apply: need 0 < C <= %d, C %% 8 == 0",
-               MAXC);
-  TTMI_REQUIRE(dy && x && mean && rstd && w && sums && dx, "ttmi_bn2d_bwd_apply: null argument");
-  hipLaunchKernelGGL(bn2d_bwd_apply_kernel, dim3(grid_ew(M * C / 8)), dim3(256), 0, s, M, C,
-                     (const bf16_t*)dy, (const bf16_t*)gate, (const bf16_t*)x, mean, rstd, w, sums,
-                     (bf16_t*)dx, dw, db);
-  return ttmi_check_launch("ttmi_bn2d_bwd_apply");
+  return bn2d_bwd_apply_t<bf16_t>("ttmi_bn2d_bwd_apply", M, C, dy, gate, x, mean, rstd, w, sums, dx, dw, db, s);
+}
+extern "C" int ttmi_bn2d_bwd_apply_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                                       const float* mean, const float* rstd, const float* w, const int64_t* sums,
+                                       float* dx, float* dw, float* db, hipStream_t s) {
+  return bn2d_bwd_apply_t<float>("ttmi_bn2d_bwd_apply_f32", M, C, dy, gate, x, mean, rstd, w, sums, dx, dw, db, s);
 }
 
 extern "C" int ttmi_bn2d_bwd(int64_t M, int C, const uint16_t* dy, const uint16_t* gate,
@@ -848,50 +973,47 @@ extern "C" int ttmi_bn2d_bwd(int64_t M, int C, const uint16_t* dy, const uint16_
   if (rc) return rc;
   return ttmi_bn2d_bwd_apply(M, C, dy, gate, x, mean, rstd, w, sums, dx, dw, db, s);
 }
+extern "C" int ttmi_bn2d_bwd_f32(int64_t M, int C, const float* dy, const float* gate, const float* x,
+                                 const float* mean, const float* rstd, const float* w, int64_t* sums,
+                                 float* g_out, float* dx, float* dw, float* db, hipStream_t s) {
+  TTMI_REQUIRE(dy && x && mean && rstd && w && sums && dx, "ttmi_bn2d_bwd_f32: null argument");
+  int rc = ttmi_bn2d_bwd_reduce_f32(M, C, dy, gate, x, mean, rstd, sums, g_out, s);
+  if (rc) return rc;
+  return ttmi_bn2d_bwd_apply_f32(M, C, dy, gate, x, mean, rstd, w, sums, dx, dw, db, s);
+}
 
 extern "C" int ttmi_maxpool_fwd(int N, int H, int W, int C, int k, int stride, int pad,
                                 const uint16_t* x, uint16_t* y, uint8_t* idx, hipStream_t s) {
-  TTMI_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && k > 0 && k * k <= 255 && stride > 0 &&
-                   pad >= 0 && pad < k, "ttmi_maxpool_fwd: bad shape");
-  TTMI_REQUIRE(x && y && idx, "ttmi_maxpool_fwd: null argument");
-  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-  if (N == 0) return TTMI_OK;
-  TTMI_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "ttmi_maxpool_fwd: tensor too large");
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for((int64_t)N * Ho * Wo * C / 8)), dim3(256), 0, s, N, H,
-                     W, C, Ho, Wo, k, stride, pad, (const bf16_t*)x, (bf16_t*)y, idx);
-  return ttmi_check_launch("ttmi_maxpool_fwd");
+  return maxpool_fwd_t<bf16_t>("ttmi_maxpool_fwd", N, H, W, C, k, stride, pad, x, y, idx, s);
+}
+extern "C" int ttmi_maxpool_fwd_f32(int N, int H, int W, int C, int k, int stride, int pad, const float* x,
+                                    float* y, uint8_t* idx, hipStream_t s) {
+  return maxpool_fwd_t<float>("ttmi_maxpool_fwd_f32", N, H, W, C, k, stride, pad, x, y, idx, s);
 }
 
 extern "C" int ttmi_maxpool_bwd(int N, int H, int W, int C, int k, int stride, int pad,
                                 const uint16_t* dy, const uint8_t* idx, uint16_t* dx, hipStream_t s) {
-  TTMI_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && k > 0 && stride > 0 && pad >= 0,
-               "ttmi_maxpool_bwd: bad shape");
-  TTMI_REQUIRE(dy && idx && dx, "ttmi_maxpool_bwd: null argument");
-  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-  if (N == 0) return TTMI_OK;
-  TTMI_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "ttmi_maxpool_bwd: tensor too large");
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((int64_t)N * H * W * C / 8)), dim3(256), 0, s, N, H, W,
-                     C, Ho, Wo, k, stride, pad, (const bf16_t*)dy, idx, (bf16_t*)dx);
-  return ttmi_check_launch("ttmi_maxpool_bwd");
+  return maxpool_bwd_t<bf16_t>("ttmi_maxpool_bwd", N, H, W, C, k, stride, pad, dy, idx, dx, s);
+}
+extern "C" int ttmi_maxpool_bwd_f32(int N, int H, int W, int C, int k, int stride, int pad, const float* dy,
+                                    const uint8_t* idx, float* dx, hipStream_t s) {
+  return maxpool_bwd_t<float>("ttmi_maxpool_bwd_f32", N, H, W, C, k, stride, pad, dy, idx, dx, s);
 }
 
 extern "C" int ttmi_avgpool_fwd(int N, int HW, int C, const uint16_t* x, uint16_t* y, hipStream_t s) {
-  TTMI_REQUIRE(N >= 0 && HW > 0 && C > 0, "ttmi_avgpool_fwd: bad shape");
-  TTMI_REQUIRE(x && y, "ttmi_avgpool_fwd: null argument");
-  if (N == 0) return TTMI_OK;
-  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(N * ((C + 63) / 64)), dim3(256), 0, s, N, HW, C, (const bf16_t*)x,
-                     (bf16_t*)y);
-  return ttmi_check_launch("ttmi_avgpool_fwd");
+  return avgpool_fwd_t<bf16_t>("ttmi_avgpool_fwd", N, HW, C, x, y, s);
+}
+extern "C" int ttmi_avgpool_fwd_f32(int N, int HW, int C, const float* x, float* y, hipStream_t s) {
+  return avgpool_fwd_t<float>("ttmi_avgpool_fwd_f32", N, HW, C, x, y, s);
 }
 
 extern "C" int ttmi_avgpool_bwd(int N, int HW, int C, const void* dy, int dy_dtype, const uint16_t* gate,
                                 uint16_t* dx, hipStream_t s) {
-  TTMI_REQUIRE(N >= 0 && HW > 0 && C > 0, "ttmi_avgpool_bwd: bad shape");
-  TTMI_REQUIRE(dy && dx, "ttmi_avgpool_bwd: null argument");
-  if (N == 0) return TTMI_OK;
-  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((int64_t)N * HW * C)), dim3(256), 0, s, N, HW, C, dy,
-                     dy_dtype == TTMI_F32, (const bf16_t*)gate, (bf16_t*)dx);
-  return ttmi_check_launch("ttmi_avgpool_bwd");
+  return avgpool_bwd_t<bf16_t>("ttmi_avgpool_bwd", N, HW, C, dy, dy_dtype, gate, dx, s);
+}
+extern "C" int ttmi_avgpool_bwd_f32(int N, int HW, int C, const void* dy, int dy_dtype, const float* gate,
+                                    float* dx, hipStream_t s) {
+  return avgpool_bwd_t<float>("ttmi_avgpool_bwd_f32", N, HW, C, dy, dy_dtype, gate, dx, s);
 }
 
 extern "C" int ttmi_stem_pool_fwd(int N, int H, int W, int C, const uint16_t* x, const int64_t* colsum,

@@ -19,6 +19,8 @@
 // (deterministic; no scattered fp32 atomics into torch's [Co][Cin][KH][KW] layout).
 // Wf = [Co][KH][KW][C] and Wd = [C][KH][KW][Co] are bf16 mirrors of torch's weight
 // (ttmi_conv_weight_prep).  FWD also accumulates Σy, Σy² per channel for the BatchNorm.
+// conv_f32_kernel (below) is the same GEMM on fp32 activations and fp32 mirrors
+// (ttmi_conv_desc.f32), on v_mfma_f32_16x16x4_f32: the reference-parity mode.
 #include "ttmi_common.h"
 
 #include <climits>
@@ -874,10 +876,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(float* __restrict__ w
 
 // Wf[co][kh][kw][c] = bf16(w[co][ci][kh][kw]) (c < Cp, zero for ci >= Cin);
 // Wd[c][kh][kw][co] likewise (c < Cin only: the padded stem never needs its input grad).
+// (T = bf16_t, or float for the fp32-storage mode's mirrors)
+template <typename T>
 __global__ __launch_bounds__(256) void conv_weight_prep_kernel(int Co, int Cin, int Cp, int KH, int KW,
                                                                const float* __restrict__ w,
-                                                               bf16_t* __restrict__ wf,
-                                                               bf16_t* __restrict__ wd) {
+                                                               T* __restrict__ wf,
+                                                               T* __restrict__ wd) {
   const int64_t n = (int64_t)Co * KH * KW * Cp;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % Cp);
@@ -886,17 +890,18 @@ __global__ __launch_bounds__(256) void conv_weight_prep_kernel(int Co, int Cin, 
     const int kh = (int)(t % KH);
     const int co = (int)(t / KH);
     const float v = c < Cin ? w[(((int64_t)co * Cin + c) * KH + kh) * KW + kw] : 0.f;
-    wf[i] = f2bf(v);
-    if (wd && c < Cin) wd[(((int64_t)c * KH + kh) * KW + kw) * Co + co] = f2bf(v);
+    stf(wf, i, v);
+    if (wd && c < Cin) stf(wd, (((int64_t)c * KH + kh) * KW + kw) * Co + co, v);
   }
 }
 
 // x NCHW fp32 [N][Cin][H][W] -> NHWC bf16 [N][H][W][Cp] (channels zero-padded).  One thread
 // per pixel: the Cin plane reads are coalesced across threads (consecutive w), the Cp-channel
 // row is written as whole 16-byte chunks.
+template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(int N, int Cin, int H, int W, int Cp,
                                                            const float* __restrict__ x,
-                                                           bf16_t* __restrict__ y) {
+                                                           T* __restrict__ y) {
   const int64_t HW = (int64_t)H * W, npix = (int64_t)N * HW;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = p / HW, hw = p - b * HW;
@@ -906,7 +911,12 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(int N, int Cin, int H
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = c0 + e < Cin ? src[(int64_t)(c0 + e) * HW] : 0.f;
-      dst[c0 / 8] = pack8(v);
+      if constexpr (sizeof(T) == 2) {
+        dst[c0 / 8] = pack8(v);
+      } else {                                            // fp32 storage: two 16-byte chunks
+        dst[c0 / 4] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+        dst[c0 / 4 + 1] = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+      }
     }
   }
 }
@@ -964,13 +974,14 @@ struct WPrepBatch {
 };
 constexpr int WP_CO = 32;
 TTMI_DEV int wp_tc(const ttmi_conv_wprep& t) { return t.KH * t.KW <= 9 ? 32 : 4; }
+template <typename E>     // mirror element: bf16_t, or float for the fp32-storage mode
 __global__ __launch_bounds__(256) void conv_weight_prep_batch_kernel(WPrepBatch b) {
   __shared__ float tile[WP_CO * (32 * 9 + 1)];
   int k = 0;
   while (k + 1 < b.n && (int)blockIdx.x >= b.blk[k + 1]) ++k;
   const ttmi_conv_wprep& t = b.it[k];
   const int j = blockIdx.x - b.blk[k];
-  bf16_t* wf = reinterpret_cast<bf16_t*>(t.wf);
+  E* wf = reinterpret_cast<E*>(t.wf);
   if (t.s2d) {                                          // 1024 elements per workgroup
     const int64_t n = (int64_t)t.Co * 16 * t.Cp;
     for (int64_t i = (int64_t)j * 1024 + threadIdx.x; i < min(n, (int64_t)(j + 1) * 1024); i += blockDim.x) {
@@ -979,7 +990,7 @@ __global__ __launch_bounds__(256) void conv_weight_prep_batch_kernel(WPrepBatch 
       const int q = cc / t.Cin, ci = cc - q * t.Cin;
       const int kh = 2 * (tap >> 2) + (q >> 1) - 1, kw = 2 * (tap & 3) + (q & 1) - 1;
       const bool ok = q < 4 && kh >= 0 && kh < 7 && kw >= 0 && kw < 7;
-      wf[i] = f2bf(ok ? t.w[(((int64_t)co * t.Cin + ci) * 7 + kh) * 7 + kw] : 0.f);
+      stf(wf, i, ok ? t.w[(((int64_t)co * t.Cin + ci) * 7 + kh) * 7 + kw] : 0.f);
     }
     return;
   }
@@ -999,15 +1010,344 @@ __global__ __launch_bounds__(256) void conv_weight_prep_batch_kernel(WPrepBatch 
     const int cl = f % TC, q = f / TC;
     const int tap = q % T, r = q / T;
     const int co = co0 + r, cc = c0 + cl;
-    if (co < t.Co && cc < t.Cp) wf[((int64_t)co * T + tap) * t.Cp + cc] = f2bf(tile[r * P + cl * T + tap]);
+    if (co < t.Co && cc < t.Cp) stf(wf, ((int64_t)co * T + tap) * t.Cp + cc, tile[r * P + cl * T + tap]);
   }
   if (t.wd) {                                           // Wd[c][tap][co]: co fastest
-    bf16_t* wd = reinterpret_cast<bf16_t*>(t.wd);
+    E* wd = reinterpret_cast<E*>(t.wd);
     for (int f = threadIdx.x; f < TC * T * WP_CO; f += blockDim.x) {
       const int r = f % WP_CO, q = f / WP_CO;
       const int tap = q % T, cl = q / T;
       const int co = co0 + r, cc = c0 + cl;
-      if (co < t.Co && cc < t.Cin) wd[((int64_t)cc * T + tap) * t.Co + co] = f2bf(tile[r * P + cl * T + tap]);
+      if (co < t.Co && cc < t.Cin) stf(wd, ((int64_t)cc * T + tap) * t.Co + co, tile[r * P + cl * T + tap]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- fp32-storage tile
+// The same implicit GEMM on fp32 NHWC activations and fp32 mirrors (ttmi_conv_desc.f32): the
+// reference-parity mode of the ResNet encoders.  conv_tile_kernel's structure — BM x BN of
+// 64/128, four waves 2x2, double-buffered LDS with a register prefetch, the same row decode,
+// parity classes and split partials — with its own fragment code: K is walked 32 floats
+// (128 B per LDS row) a step and multiplied by v_mfma_f32_16x16x4_f32 (exact fp32 products,
+// fp32 accumulate).
+//   FWD / DGRAD image: [row][32 floats], pitch 128 B, the row's eight 16-byte chunks XOR-
+//     swizzled by (row >> 1) & 7.  A lane (i = lane & 15, g = lane >> 4) reads chunk 4c + g of
+//     row i as one ds_read_b128 (four MFMAs' operands; k permuted alike on both sides): in
+//     each 16-lane service group the even rows land in banks 0-31, the odd rows in 32-63, and
+//     the swizzle gives the eight rows of a parity eight distinct chunk slots — no conflict.
+//     (Padding the pitch alone cannot do that: the groups mix g and g + 1 over all 16 rows.)
+//   WGRAD image: [k = pixel][row], pitch BM·4 + 64 B.  The 16x16x4 MFMA takes one float per
+//     lane (row i, k = g), so the transposed operand is a plain ds_read_b32 at
+//     [4q + g][row0 + i]: 16 lanes read 64 contiguous bytes, and the pitch puts k rows g and
+//     g + 1 sixteen banks apart (the 32-lane service groups hold two k rows).
+// Epilogues as conv_tile_kernel's with float4 stores; FWD accumulates the BatchNorm Σy, Σy² in
+// the same int64 fixed point, replica rows and order, so the mode is bit-reproducible.
+namespace f32c {
+constexpr int KS = 32;                                  // floats of k per step
+TTMI_DEV uint4 ldg(const float* p, bool ok) {
+  return ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0, 0, 0, 0);
+}
+TTMI_DEV int swz(int r) { return (r >> 1) & 7; }
+TTMI_DEV uint4 frag(const char* s, int row, int c, int g) {
+  return lds16(s + row * 128 + (((4 * c + g) ^ swz(row)) << 4));
+}
+}  // namespace f32c
+
+template <int MODE, int BM, int BN>
+__global__ __launch_bounds__(256) void conv_f32_kernel(ConvArgs a) {
+  using namespace f32c;
+  constexpr bool WG = MODE == 2;
+  constexpr int CA = BM / 32, CB = BN / 32;             // 16-B chunks per thread per stage
+  constexpr int WM = BM / 2, WN = BN / 2, FM = WM / 16, FN = WN / 16;
+  constexpr int PTA = BM * 4 + 64, PTB = BN * 4 + 64;   // [k][row] pitches (WGRAD)
+  constexpr int SA = WG ? KS * PTA : BM * 128;
+  constexpr int SB = WG ? KS * PTB : BN * 128;
+  constexpr int STAGE = SA + SB;
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const float* ax = reinterpret_cast<const float*>(a.x);
+  const float* ady = reinterpret_cast<const float*>(a.dy);
+  const float* aw = reinterpret_cast<const float*>(a.w);
+
+  const int gx = (a.GN + BN - 1) / BN;
+  int t = blockIdx.x;
+  if ((gridDim.x & 7) == 0) t = (t & 7) * (gridDim.x >> 3) + (t >> 3);
+  const int n0 = (t % gx) * BN, m0 = (t / gx) * BM;
+  const int cls = MODE == 1 ? (int)blockIdx.y : 0;
+  const int GM = MODE == 1 ? a.cM[cls] : a.GM;
+  const int GK = MODE == 1 ? a.cK[cls] : a.GK;
+  if (m0 >= GM) return;                                  // DGRAD: smaller parity class
+  const int kbeg = WG ? (int)blockIdx.y * a.k_split : 0;
+  const int kend = WG ? min(GK, kbeg + a.k_split) : GK;
+
+  // ---- per-thread gather state, decoded once (as conv_tile_kernel; chunks are 4 floats)
+  const int kk = (tid & 7) * 4;                          // FWD/DGRAD: k offset of my chunks
+  int rh[CA], rw[CA];
+  const float* rbase[CA];
+  int bkh[CB], bkw[CB], bci[CB];                         // WGRAD: tap/channel of my B chunks
+  bool bok[CB];
+  if constexpr (MODE == 0) {
+#pragma unroll
+    for (int c = 0; c < CA; ++c) {
+      const int m = m0 + (tid >> 3) + 32 * c;
+      rh[c] = INT_MIN / 2; rw[c] = 0; rbase[c] = ax;
+      if (m < GM) {
+        const int q = fq(m, a.fWo), wo = m - q * a.Wo;
+        const int n = fq(q, a.fHo), ho = q - n * a.Ho;
+        rh[c] = ho * a.S - a.P;
+        rw[c] = wo * a.S - a.P;
+        rbase[c] = ax + (int64_t)n * a.H * a.W * a.C;
+      }
+    }
+  } else if constexpr (MODE == 1) {
+#pragma unroll
+    for (int c = 0; c < CA; ++c) {
+      const int m = m0 + (tid >> 3) + 32 * c;
+      rh[c] = INT_MIN / 2; rw[c] = 0; rbase[c] = ady;
+      if (m < GM) {
+        const int q = fq(m, a.cfW[cls]), ww = m - q * a.cWc[cls];
+        const int n = fq(q, a.cfH[cls]), hh = q - n * a.cHc[cls];
+        rh[c] = hh + a.coffh[cls];
+        rw[c] = ww + a.coffw[cls];
+        rbase[c] = ady + (int64_t)n * a.Ho * a.Wo * a.Co;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+      const int kc = n0 + ((tid + 256 * c) % (BN / 4)) * 4;
+      bok[c] = kc < a.GN;
+      const int tap = fq(kc, a.fC);
+      bci[c] = kc - tap * a.C;
+      bkh[c] = fq(tap, a.fKW);
+      bkw[c] = tap - bkh[c] * a.KW;
+    }
+  }
+
+  uint4 ra[CA], rb[CB];
+  auto load = [&](int k0) {
+    if constexpr (MODE == 0) {
+      const int k = k0 + kk;
+      const bool kin = k < GK;
+      const int tap = fq(k, a.fC), ci = k - tap * a.C;
+      const int kh = fq(tap, a.fKW), kw = tap - kh * a.KW;
+#pragma unroll
+      for (int c = 0; c < CA; ++c) {
+        const int hi = rh[c] + kh, wi = rw[c] + kw;
+        const bool ok = kin && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
+        ra[c] = ldg(rbase[c] + ((int64_t)hi * a.W + wi) * a.C + ci, ok);
+      }
+#pragma unroll
+      for (int c = 0; c < CB; ++c) {
+        const int n = n0 + (tid >> 3) + 32 * c;
+        rb[c] = ldg(aw + (int64_t)n * GK + k, kin && n < a.GN);
+      }
+    } else if constexpr (MODE == 1) {
+      const int k = k0 + kk;
+      const bool kin = k < GK;
+      const int tt = fq(k, a.fCo), co = k - tt * a.Co;
+      const int i = fq(tt, a.cfnkw[cls]), j = tt - i * a.cnkw[cls];
+#pragma unroll
+      for (int c = 0; c < CA; ++c) {
+        const int ho = rh[c] - i, wo = rw[c] - j;
+        const bool ok = kin && (unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo;
+        ra[c] = ldg(rbase[c] + ((int64_t)ho * a.Wo + wo) * a.Co + co, ok);
+      }
+      const int kh = a.ckh0[cls] + a.S * i, kw = a.ckw0[cls] + a.S * j;
+      const int64_t wcol = (int64_t)(kh * a.KW + kw) * a.Co + co;
+      const int64_t wrow = (int64_t)a.KH * a.KW * a.Co;
+#pragma unroll
+      for (int c = 0; c < CB; ++c) {
+        const int n = n0 + (tid >> 3) + 32 * c;
+        rb[c] = ldg(aw + n * wrow + wcol, kin && n < a.GN);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < CA; ++c) {
+        const int idx = tid + 256 * c;
+        const int p = k0 + idx / (BM / 4), co = m0 + (idx % (BM / 4)) * 4;
+        ra[c] = ldg(ady + (int64_t)p * a.Co + co, p < kend && co < a.GM);
+      }
+#pragma unroll
+      for (int c = 0; c < CB; ++c) {
+        const int p = k0 + (tid + 256 * c) / (BN / 4);
+        const int q = fq(p, a.fWo), wo = p - q * a.Wo;
+        const int n = fq(q, a.fHo), ho = q - n * a.Ho;
+        const int hi = ho * a.S - a.P + bkh[c], wi = wo * a.S - a.P + bkw[c];
+        const bool ok = p < kend && bok[c] && (unsigned)hi < (unsigned)a.H &&
+                        (unsigned)wi < (unsigned)a.W;
+        rb[c] = ldg(ax + (((int64_t)n * a.H + hi) * a.W + wi) * a.C + bci[c], ok);
+      }
+    }
+  };
+  auto store = [&](char* s) {
+    char* sa = s;
+    char* sb = s + SA;
+    if constexpr (!WG) {
+#pragma unroll
+      for (int c = 0; c < CA; ++c) {
+        const int r = (tid >> 3) + 32 * c;
+        *reinterpret_cast<uint4*>(sa + r * 128 + (((tid & 7) ^ swz(r)) << 4)) = ra[c];
+      }
+#pragma unroll
+      for (int c = 0; c < CB; ++c) {
+        const int r = (tid >> 3) + 32 * c;
+        *reinterpret_cast<uint4*>(sb + r * 128 + (((tid & 7) ^ swz(r)) << 4)) = rb[c];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < CA; ++c) {
+        const int idx = tid + 256 * c;
+        *reinterpret_cast<uint4*>(sa + (idx / (BM / 4)) * PTA + (idx % (BM / 4)) * 16) = ra[c];
+      }
+#pragma unroll
+      for (int c = 0; c < CB; ++c) {
+        const int idx = tid + 256 * c;
+        *reinterpret_cast<uint4*>(sb + (idx / (BN / 4)) * PTB + (idx % (BN / 4)) * 16) = rb[c];
+      }
+    }
+  };
+
+  f32x4_t acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int li = lane & 15, lg = lane >> 4;
+  if (kbeg < kend) {
+    load(kbeg);
+    store(smem);
+  }
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kbeg; k0 < kend; k0 += KS) {
+    const bool more = k0 + KS < kend;
+    if (more) load(k0 + KS);
+    const char* sa = smem + buf * STAGE;
+    const char* sb = sa + SA;
+    if constexpr (!WG) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        uint4 af[FM], bfr[FN];
+#pragma unroll
+        for (int i = 0; i < FM; ++i) af[i] = frag(sa, wm * WM + i * 16 + li, c, lg);
+#pragma unroll
+        for (int j = 0; j < FN; ++j) bfr[j] = frag(sb, wn * WN + j * 16 + li, c, lg);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) Mma<float>::run(acc[i][j], bfr[j], af[i]);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < KS / 4; ++q) {
+        float af[FM], bfr[FN];
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+          af[i] = *reinterpret_cast<const float*>(sa + (4 * q + lg) * PTA + (wm * WM + i * 16 + li) * 4);
+#pragma unroll
+        for (int j = 0; j < FN; ++j)
+          bfr[j] = *reinterpret_cast<const float*>(sb + (4 * q + lg) * PTB + (wn * WN + j * 16 + li) * 4);
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bfr[j], af[i], acc[i][j], 0, 0, 0);
+      }
+    }
+    if (more) store(smem + (buf ^ 1) * STAGE);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // ---- epilogue: lane holds C[m][n..n+3], m = row + (lane & 15), n = col + 4*(lane >> 4)
+  if constexpr (MODE == 2) {
+    float* ws = a.ws + (int64_t)blockIdx.y * a.GM * a.GN;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const int m = m0 + wm * WM + i * 16 + li;
+      if (m >= a.GM) continue;
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const int n = n0 + wn * WN + j * 16 + 4 * lg;
+        if (n < a.GN) *reinterpret_cast<f32x4_t*>(ws + (int64_t)m * a.GN + n) = acc[i][j];
+      }
+    }
+    return;
+  }
+  int64_t orow[FM];                                       // output pixel of each row
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    const int m = m0 + wm * WM + i * 16 + li;
+    orow[i] = -1;
+    if (m < GM) {
+      if constexpr (MODE == 1) {
+        const int q = fq(m, a.cfW[cls]), ww = m - q * a.cWc[cls];
+        const int n = fq(q, a.cfH[cls]), hh = q - n * a.cHc[cls];
+        const int ph = cls / a.S, pw = cls - ph * a.S;
+        orow[i] = ((int64_t)n * a.H + hh * a.S + ph) * a.W + ww * a.S + pw;
+      } else {
+        orow[i] = m;
+      }
+    }
+  }
+  const float* addend = reinterpret_cast<const float*>(a.addend);
+  float cs[FN][4], cq[FN][4];
+#pragma unroll
+  for (int j = 0; j < FN; ++j) {
+    const int n = n0 + wn * WN + j * 16 + 4 * lg;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cs[j][e] = cq[j][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      if (orow[i] < 0 || n >= a.GN) continue;
+      f32x4_t o = acc[i][j];
+      if (MODE == 1 && addend) o += *reinterpret_cast<const f32x4_t*>(addend + orow[i] * a.GN + n);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { cs[j][e] += o[e]; cq[j][e] += o[e] * o[e]; }
+      *reinterpret_cast<f32x4_t*>(static_cast<float*>(a.out) + orow[i] * a.GN + n) = o;
+    }
+  }
+  if (MODE == 0 && a.colsum) {
+    // BatchNorm column statistics, exactly conv_tile_kernel's reduction: registers, the 16 row
+    // lanes, the two row-waves through LDS, then one int64 fixed-point add per column per
+    // workgroup into replica row blockIdx.x % TTMI_CONV_STAT_REPS
+    float* red = reinterpret_cast<float*>(smem);        // [2][BN]; the K loop has drained
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {
+          cs[j][e] += __shfl_xor(cs[j][e], off, 64);
+          cq[j][e] += __shfl_xor(cq[j][e], off, 64);
+        }
+    if (wm == 1 && li == 0) {
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int col = wn * WN + j * 16 + 4 * lg + e;
+          red[col] = cs[j][e];
+          red[BN + col] = cq[j][e];
+        }
+    }
+    __syncthreads();
+    if (wm == 0 && li == 0) {
+      const int rep = blockIdx.x % TTMI_CONV_STAT_REPS;
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int col = wn * WN + j * 16 + 4 * lg + e;
+          const int n = n0 + col;
+          if (n < a.GN) {
+            fx_add(a.colsum + (int64_t)rep * a.GN + n, cs[j][e] + red[col], TTMI_FX_STAT);
+            fx_add(a.colsumsq + (int64_t)rep * a.GN + n, cq[j][e] + red[BN + col], TTMI_FX_STAT);
+          }
+        }
     }
   }
 }
@@ -1021,9 +1361,19 @@ extern "C" int ttmi_conv_weight_prep(int Co, int Cin, int Cp, int KH, int KW, co
   TTMI_REQUIRE(Co > 0 && Cin > 0 && Cp >= Cin && Cp % 8 == 0 && KH > 0 && KW > 0,
                "ttmi_conv_weight_prep: bad shape");
   TTMI_REQUIRE(w && wf, "ttmi_conv_weight_prep: null argument");
-  hipLaunchKernelGGL(conv_weight_prep_kernel, dim3(grid1((int64_t)Co * KH * KW * Cp)), dim3(256), 0, s,
+  hipLaunchKernelGGL(conv_weight_prep_kernel<bf16_t>, dim3(grid1((int64_t)Co * KH * KW * Cp)), dim3(256), 0, s,
                      Co, Cin, Cp, KH, KW, w, wf, wd);
   return ttmi_check_launch("ttmi_conv_weight_prep");
+}
+
+extern "C" int ttmi_conv_weight_prep_f32(int Co, int Cin, int Cp, int KH, int KW, const float* w,
+                                         float* wf, float* wd, hipStream_t s) {
+  TTMI_REQUIRE(Co > 0 && Cin > 0 && Cp >= Cin && Cp % 8 == 0 && KH > 0 && KW > 0,
+               "ttmi_conv_weight_prep_f32: bad shape");
+  TTMI_REQUIRE(w && wf, "ttmi_conv_weight_prep_f32: null argument");
+  hipLaunchKernelGGL(conv_weight_prep_kernel<float>, dim3(grid1((int64_t)Co * KH * KW * Cp)), dim3(256), 0, s,
+                     Co, Cin, Cp, KH, KW, w, wf, wd);
+  return ttmi_check_launch("ttmi_conv_weight_prep_f32");
 }
 
 extern "C" int ttmi_nchw_to_nhwc(int N, int Cin, int H, int W, int Cp, const float* x, uint16_t* y,
@@ -1031,9 +1381,19 @@ extern "C" int ttmi_nchw_to_nhwc(int N, int Cin, int H, int W, int Cp, const flo
   TTMI_REQUIRE(N >= 0 && Cin > 0 && Cp >= Cin && Cp % 8 == 0 && H > 0 && W > 0, "ttmi_nchw_to_nhwc: bad shape");
   TTMI_REQUIRE(x && y, "ttmi_nchw_to_nhwc: null argument");
   if (N == 0) return TTMI_OK;
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid1((int64_t)N * H * W)), dim3(256), 0, s, N, Cin, H,
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(grid1((int64_t)N * H * W)), dim3(256), 0, s, N, Cin, H,
                      W, Cp, x, y);
   return ttmi_check_launch("ttmi_nchw_to_nhwc");
+}
+
+extern "C" int ttmi_nchw_to_nhwc_f32(int N, int Cin, int H, int W, int Cp, const float* x, float* y,
+                                     hipStream_t s) {
+  TTMI_REQUIRE(N >= 0 && Cin > 0 && Cp >= Cin && Cp % 8 == 0 && H > 0 && W > 0, "ttmi_nchw_to_nhwc_f32: bad shape");
+  TTMI_REQUIRE(x && y, "ttmi_nchw_to_nhwc_f32: null argument");
+  if (N == 0) return TTMI_OK;
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid1((int64_t)N * H * W)), dim3(256), 0, s, N, Cin, H,
+                     W, Cp, x, y);
+  return ttmi_check_launch("ttmi_nchw_to_nhwc_f32");
 }
 
 extern "C" int ttmi_conv_weight_prep_batch(int n, const ttmi_conv_wprep* items, hipStream_t s) {
@@ -1046,6 +1406,9 @@ extern "C" int ttmi_conv_weight_prep_batch(int n, const ttmi_conv_wprep* items, 
       const ttmi_conv_wprep& t = items[base + k];
       TTMI_REQUIRE(t.Co > 0 && t.Cin > 0 && t.Cp % 8 == 0 && t.w && t.wf, "ttmi_conv_weight_prep_batch: item %d",
                    base + k);
+      TTMI_REQUIRE(t.f32 == items[base].f32 && (t.f32 == 0 || t.f32 == 1),
+                   "ttmi_conv_weight_prep_batch: item %d: f32 is 0 or 1, the same for all items", base + k);
+      TTMI_REQUIRE(!(t.f32 && t.s2d), "ttmi_conv_weight_prep_batch: item %d: no fp32 space-to-depth mirror", base + k);
       TTMI_REQUIRE(t.s2d ? (t.KH == 7 && t.KW == 7 && t.Cp >= 4 * t.Cin)
                          : (t.Cp >= t.Cin && t.KH > 0 && t.KW > 0 && t.KH * t.KW <= 49),
                    "ttmi_conv_weight_prep_batch: item %d shape", base + k);
@@ -1056,7 +1419,10 @@ extern "C" int ttmi_conv_weight_prep_batch(int n, const ttmi_conv_wprep* items, 
       TTMI_REQUIRE(b.blk[k] + nb < (1ll << 30), "ttmi_conv_weight_prep_batch: too many tiles");
       b.blk[k + 1] = b.blk[k] + (int)nb;
     }
-    hipLaunchKernelGGL(conv_weight_prep_batch_kernel, dim3((unsigned)b.blk[b.n]), dim3(256), 0, s, b);
+    if (items[base].f32)
+      hipLaunchKernelGGL(conv_weight_prep_batch_kernel<float>, dim3((unsigned)b.blk[b.n]), dim3(256), 0, s, b);
+    else
+      hipLaunchKernelGGL(conv_weight_prep_batch_kernel<bf16_t>, dim3((unsigned)b.blk[b.n]), dim3(256), 0, s, b);
     const int rc = ttmi_check_launch("ttmi_conv_weight_prep_batch");
     if (rc) return rc;
   }
@@ -1137,11 +1503,18 @@ struct ConvPlan {
   bool dma;                 // on the LDS-DMA kernels (conv_dma_kernel / conv_wgrad_dma_kernel)
   int s2d;                  // space-to-depth stem (modes 3 / 4)
   int64_t ws_bytes;
+  bool f32;                 // fp32 storage (ttmi_conv_desc.f32): conv_f32_kernel
 };
 
 int conv_plan(const ttmi_conv_desc* d, ConvPlan* pl) {
   TTMI_REQUIRE(d != nullptr, "ttmi_conv2d: null descriptor");
   TTMI_REQUIRE(d->mode >= 0 && d->mode <= 4, "ttmi_conv2d: bad mode");
+  TTMI_REQUIRE(d->f32 == 0 || d->f32 == 1, "ttmi_conv2d: f32 must be 0 (bf16 storage) or 1 (fp32 storage)");
+  if (d->f32) {
+    // the fp32 mode is the generic tile only: no space-to-depth stem, no fused BN reduction
+    TTMI_REQUIRE(d->mode <= 2, "ttmi_conv2d: the space-to-depth stem modes (3 / 4) have no fp32-storage kernel");
+    TTMI_REQUIRE(!d->bn_sums, "ttmi_conv2d: bn_sums (DGRAD-fused BatchNorm reduction) has no fp32-storage kernel");
+  }
   if (d->mode >= 3) {
     // space-to-depth stem: the descriptor states the 7x7/2/3 conv on the image; run the
     // equivalent 4x4/1 conv (pad 2 top/left) over ttmi_stem_s2d's [N][H/2][W/2][C] input
@@ -1206,13 +1579,14 @@ int conv_plan(const ttmi_conv_desc* d, ConvPlan* pl) {
   pl->ws_bytes = 0;
   pl->dma = false;
   pl->s2d = 0;
+  pl->f32 = d->f32 != 0;
   if (d->mode == 0) {
     a.GM = (int)Mo; a.GN = d->Co; a.GK = d->KH * d->KW * d->C;
     pl->bn = d->Co % 128 == 0 ? 128 : 64;
     pl->bm = 128;
     if (((a.GM + 127) / 128) * (a.GN / pl->bn) < 512) pl->bm = 64;
     if (forced_bm()) pl->bm = forced_bm();
-    pl->dma = use_dma(((int64_t)a.GM + 255) / 256 * (a.GN / pl->bn), d->Co);
+    pl->dma = !pl->f32 && use_dma(((int64_t)a.GM + 255) / 256 * (a.GN / pl->bn), d->Co);
   } else if (d->mode == 1) {
     TTMI_REQUIRE(d->Cin == d->C, "ttmi_conv2d: DGRAD needs unpadded channels (Cin == C)");
     TTMI_REQUIRE(d->Co % 64 == 0, "ttmi_conv2d: DGRAD needs Co %% 64 == 0");
@@ -1240,7 +1614,7 @@ int conv_plan(const ttmi_conv_desc* d, ConvPlan* pl) {
     if (forced_bm()) pl->bm = forced_bm();
     int64_t dt = 0;
     for (int c = 0; c < S * S; ++c) dt += ((int64_t)a.cM[c] + 255) / 256 * (a.GN / pl->bn);
-    pl->dma = use_dma(dt, d->C);
+    pl->dma = !pl->f32 && use_dma(dt, d->C);
   } else {
     a.GM = d->Co; a.GN = d->KH * d->KW * d->C; a.GK = (int)Mo;
     pl->bm = d->Co % 128 == 0 ? 128 : 64;
@@ -1252,7 +1626,7 @@ int conv_plan(const ttmi_conv_desc* d, ConvPlan* pl) {
     a.k_split = (int)(per * 64);
     pl->splits = (int)((ksteps + per - 1) / per);
     TTMI_REQUIRE(pl->splits <= 65535, "ttmi_conv2d: too many splits");
-    pl->dma = d->Co % 64 == 0 && forced_dma() != 0;
+    pl->dma = !pl->f32 && d->Co % 64 == 0 && forced_dma() != 0;
     pl->ws_bytes = (int64_t)pl->splits * a.GM * a.GN * 4;
   }
   return TTMI_OK;
@@ -1261,6 +1635,19 @@ int conv_plan(const ttmi_conv_desc* d, ConvPlan* pl) {
 template <int MODE>
 void launch_conv(const ConvPlan& pl, hipStream_t s) {
   const ConvArgs& a = pl.a;
+  if (pl.f32) {
+    const int64_t tiles = (int64_t)((a.GN + pl.bn - 1) / pl.bn) * ((a.GM + pl.bm - 1) / pl.bm);
+    const dim3 grid((unsigned)tiles, MODE == 1 ? (unsigned)(a.S * a.S) : (unsigned)pl.splits);
+    if (pl.bm == 128 && pl.bn == 128)
+      hipLaunchKernelGGL((conv_f32_kernel<MODE, 128, 128>), grid, dim3(256), 0, s, a);
+    else if (pl.bm == 128)
+      hipLaunchKernelGGL((conv_f32_kernel<MODE, 128, 64>), grid, dim3(256), 0, s, a);
+    else if (pl.bn == 128)
+      hipLaunchKernelGGL((conv_f32_kernel<MODE, 64, 128>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((conv_f32_kernel<MODE, 64, 64>), grid, dim3(256), 0, s, a);
+    return;
+  }
   if constexpr (MODE == 2) if (pl.dma) {
     const int tn = (a.GN + 127) / 128, tiles = ((a.GM + pl.bm - 1) / pl.bm) * tn;
     const dim3 grid((unsigned)((int64_t)tiles * pl.splits));

@@ -63,19 +63,24 @@ class MultimodalItemEncoder(nn.Module):
                  text_dim: int = 128, tabular_dim: int = 128, use_lora: bool = True, *,
                  precomputed_modalities: bool = False, with_text: bool = True,
                  text_cfg: Optional[TextCfg] = None,
-                 compute_dtype: torch.dtype = torch.bfloat16):
+                 compute_dtype: torch.dtype = torch.bfloat16,
+                 encoder_dtype: torch.dtype = torch.bfloat16):
+        """compute_dtype: GEMM operand dtype of the fusion head.  encoder_dtype: activation
+        storage of the raw audio / visual / tabular encoders (cnn.py; torch.float32 is the
+        reference-parity mode); the text encoder stays bf16.  The two are independent."""
         super().__init__()
         self.precomputed_modalities = precomputed_modalities
         self.with_text = with_text and not precomputed_modalities
+        self.encoder_dtype = cnn.check_dtype(encoder_dtype, "MultimodalItemEncoder(encoder_dtype)")
         if not precomputed_modalities:
-            self.audio_encoder = cnn.AudioEncoder(embedding_dim=audio_dim)
-            self.visual_encoder = cnn.VisualEncoder(embedding_dim=visual_dim)
+            self.audio_encoder = cnn.AudioEncoder(embedding_dim=audio_dim, dtype=encoder_dtype)
+            self.visual_encoder = cnn.VisualEncoder(embedding_dim=visual_dim, dtype=encoder_dtype)
             if self.with_text:                                  # cfg 4
                 self.text_encoder = TextEncoder(model_name=text_model_name,
                                                 embedding_dim=text_dim, use_lora=use_lora,
                                                 cfg=text_cfg)
             self.tabular_encoder = cnn.TabularEncoder(input_dim=tabular_input_dim,
-                                                      embedding_dim=tabular_dim)
+                                                      embedding_dim=tabular_dim, dtype=encoder_dtype)
         self.embedding_dim = embedding_dim
         self.modal_dims = (audio_dim, visual_dim, text_dim, tabular_dim)
         self.compute_dtype = compute_dtype

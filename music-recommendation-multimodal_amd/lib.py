@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libttmi.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_i, c_i64, c_u64, c_f, c_p = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
                                ctypes.c_void_p)
@@ -63,13 +63,14 @@ class ConvDesc(ctypes.Structure):
                 ("colsum", c_p), ("colsumsq", c_p), ("workspace", c_p),
                 ("workspace_bytes", ctypes.c_int64),
                 ("bn_gate", c_p), ("bn_x", c_p), ("bn_mean", c_p), ("bn_rstd", c_p),
-                ("bn_sums", c_p)]
+                ("bn_sums", c_p),
+                ("f32", c_i)]        # ABI 23: 1 = fp32 activations and mirrors (0 = bf16)
 
 
 class ConvWPrep(ctypes.Structure):
     """ttmi_conv_wprep (include/ttmi.h)."""
     _fields_ = [("Co", c_i), ("Cin", c_i), ("Cp", c_i), ("KH", c_i), ("KW", c_i), ("s2d", c_i),
-                ("w", c_p), ("wf", c_p), ("wd", c_p)]
+                ("w", c_p), ("wf", c_p), ("wd", c_p), ("f32", c_i)]
 
 
 class DisAttnDesc(ctypes.Structure):
@@ -353,6 +354,8 @@ SIGNATURES = {
     "ttmi_conv2d_workspace": (ctypes.c_int64, [c_p]),
     "ttmi_conv_weight_prep": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "ttmi_nchw_to_nhwc": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "ttmi_conv_weight_prep_f32": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "ttmi_nchw_to_nhwc_f32": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "ttmi_conv_weight_prep_batch": (c_i, [c_i, c_p, c_p]),
     "ttmi_stem_s2d": (c_i, [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "ttmi_stem_weight_prep": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p]),
@@ -369,6 +372,16 @@ SIGNATURES = {
                                  c_p, c_p, c_p]),
     "ttmi_avgpool_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p]),
     "ttmi_avgpool_bwd": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p]),
+    # fp32-storage forms (ABI 23): the same argument lists as the bf16 entry points above
+    "ttmi_bn2d_fwd_f32": (c_i, [c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i,
+                                c_p, c_p, c_p, c_p]),
+    "ttmi_bn2d_bwd_f32": (c_i, [c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "ttmi_bn2d_bwd_reduce_f32": (c_i, [c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "ttmi_bn2d_bwd_apply_f32": (c_i, [c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "ttmi_maxpool_fwd_f32": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "ttmi_maxpool_bwd_f32": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "ttmi_avgpool_fwd_f32": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p]),
+    "ttmi_avgpool_bwd_f32": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p]),
     "ttmi_l2norm_fwd": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p]),
     "ttmi_l2norm_bwd": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ttmi_rowce_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i64, c_f, c_p, c_p, c_p, c_p]),

@@ -572,6 +572,16 @@ CONV_STAT_REPS = 16    # TTMI_CONV_STAT_REPS: BatchNorm column stats are [16][C]
 ATTN_LMAX = 2048       # TTMI_ATTN_LMAX: longest sequence the attention kernels take
 
 
+def _act_f32(who: str, *ts: Optional[Tensor]) -> bool:
+    """Storage dtype of a conv / BatchNorm2d / pool call's activations: True for fp32 (the
+    ``_f32`` kernels), False for bf16.  Every given tensor must share it (TypeError)."""
+    dts = {t.dtype for t in ts if t is not None}
+    if len(dts) != 1 or not dts <= {torch.bfloat16, torch.float32}:
+        raise TypeError(f"{who}: activations must be all bf16 or all fp32, got "
+                        f"{sorted(str(d) for d in dts)}")
+    return dts.pop() == torch.float32
+
+
 def conv2d(mode: int, N: int, H: int, W: int, C: int, Cin: int, Co: int, k: int, stride: int,
            pad: int, *, x: Optional[Tensor] = None, dy: Optional[Tensor] = None,
            w: Optional[Tensor] = None, out: Tensor, addend: Optional[Tensor] = None,
@@ -581,6 +591,9 @@ def conv2d(mode: int, N: int, H: int, W: int, C: int, Cin: int, Co: int, k: int,
     DGRAD ``bn`` = (gate, x, mean, rstd, sums): the backward reduction of the BatchNorm(+ReLU)
     that produced the conv input, fused into the epilogue (out then holds the gated g)."""
     Ho, Wo = conv_out_hw(H, W, k, stride, pad)
+    # storage dtype from the tensors (WGRAD's out is the fp32 torch-layout gradient either way)
+    f32 = _act_f32("conv2d", x, dy, w, addend, out if mode in (FWD, DGRAD, STEM_FWD) else None,
+                   *((bn[0], bn[1]) if bn is not None else ()))
     xn = N * (H // 2) * (W // 2) * C if mode in (STEM_FWD, STEM_WGRAD) else N * H * W * C
     need = {"x": (x, xn), "dy": (dy, N * Ho * Wo * Co),
             "colsum": (colsum, CONV_STAT_REPS * Co), "colsumsq": (colsumsq, CONV_STAT_REPS * Co)}
@@ -604,6 +617,7 @@ def conv2d(mode: int, N: int, H: int, W: int, C: int, Cin: int, Co: int, k: int,
     d.stride, d.pad = stride, pad
     d.x, d.dy, d.w, d.out, d.addend = _p(x), _p(dy), _p(w), _p(out), _p(addend)
     d.colsum, d.colsumsq = _p(colsum), _p(colsumsq)
+    d.f32 = int(f32)
     if bn is not None:
         if mode != DGRAD:
             raise ValueError("conv2d: bn (fused BatchNorm-backward reduction) is a DGRAD option")
@@ -630,25 +644,31 @@ def conv_weight_prep(w: Tensor, Cp: int, wf: Tensor, wd: Optional[Tensor] = None
     """bf16 GEMM mirrors of a torch Conv2d weight [Co, Cin, k, k]: wf [Co, k, k, Cp],
     wd [Cin, k, k, Co]."""
     Co, Cin, KH, KW = w.shape
-    call("ttmi_conv_weight_prep", Co, Cin, Cp, KH, KW, _p(w), _p(wf), _p(wd), _s())
+    f32 = _act_f32("conv_weight_prep", wf, wd)
+    call("ttmi_conv_weight_prep_f32" if f32 else "ttmi_conv_weight_prep", Co, Cin, Cp, KH, KW, _p(w),
+         _p(wf), _p(wd), _s())
 
 
 def conv_weight_prep_batch(items) -> None:
     """All mirrors in one launch (ttmi_conv_weight_prep_batch): items = [(w, Cp, wf, wd, s2d)]
-    with w torch's fp32 [Co, Cin, k, k]; s2d: the stem's 4x4 space-to-depth mirror."""
+    with w torch's fp32 [Co, Cin, k, k]; s2d: the stem's 4x4 space-to-depth mirror.  The mirrors
+    of one call are all bf16 or all fp32."""
+    f32 = _act_f32("conv_weight_prep_batch", *[t for it in items for t in (it[2], it[3])]) if items else False
     arr = (_L.ConvWPrep * max(1, len(items)))()
     for i, (w, Cp, wf, wd, s2d) in enumerate(items):
         Co, Cin, KH, KW = w.shape
         n = Co * (16 if s2d else KH * KW) * Cp
         if wf.numel() < n or (wd is not None and wd.numel() < Co * Cin * KH * KW) or not w.is_contiguous():
             raise ValueError(f"conv_weight_prep_batch: item {i} buffers / layout")
-        arr[i] = _L.ConvWPrep(Co, Cin, Cp, KH, KW, int(s2d), w.data_ptr(), wf.data_ptr(), _p(wd) or 0)
+        arr[i] = _L.ConvWPrep(Co, Cin, Cp, KH, KW, int(s2d), w.data_ptr(), wf.data_ptr(), _p(wd) or 0,
+                              int(f32))
     call("ttmi_conv_weight_prep_batch", len(items), ctypes.addressof(arr), _s())
 
 
 def nchw_to_nhwc(x: Tensor, Cp: int, y: Tensor) -> Tensor:
     N, Cin, H, W = x.shape
-    call("ttmi_nchw_to_nhwc", N, Cin, H, W, Cp, _p(x), _p(y), _s())
+    f32 = _act_f32("nchw_to_nhwc", y)
+    call("ttmi_nchw_to_nhwc_f32" if f32 else "ttmi_nchw_to_nhwc", N, Cin, H, W, Cp, _p(x), _p(y), _s())
     return y
 
 
@@ -681,12 +701,13 @@ def bn2d_fwd(x: Tensor, colsum: Optional[Tensor], colsumsq: Optional[Tensor], w:
              momentum: float = 0.1) -> Tensor:
     C = x.shape[-1]
     M = x.numel() // C
+    f32 = _act_f32("bn2d_fwd", x, y, residual)
     for name, t in (("colsum", colsum), ("colsumsq", colsumsq)):
         if t is not None and (t.numel() < CONV_STAT_REPS * C or t.dtype != torch.int64):
             raise ValueError(f"bn2d_fwd: {name} needs [{CONV_STAT_REPS}][{C}] int64 replica rows")
     if y.numel() < x.numel() or (residual is not None and residual.numel() < x.numel()):
         raise ValueError("bn2d_fwd: y / residual smaller than x")
-    call("ttmi_bn2d_fwd", M, C, _p(x), _p(colsum), _p(colsumsq), _p(w), _p(b), eps, momentum,
+    call("ttmi_bn2d_fwd_f32" if f32 else "ttmi_bn2d_fwd", M, C, _p(x), _p(colsum), _p(colsumsq), _p(w), _p(b), eps, momentum,
          _p(running_mean), _p(running_var), _p(num_batches), _p(residual), int(relu), _p(y),
          _p(save_mean), _p(save_rstd), _s())
     return y
@@ -697,12 +718,13 @@ def bn2d_bwd(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, w: Tensor, sums:
              gate: Optional[Tensor] = None, g_out: Optional[Tensor] = None) -> Tensor:
     C = x.shape[-1]
     M = x.numel() // C
+    f32 = _act_f32("bn2d_bwd", dy, x, dx, gate, g_out)
     if sums.numel() < 2 * CONV_STAT_REPS * C or sums.dtype != torch.int64:
         raise ValueError(f"bn2d_bwd: sums needs [{CONV_STAT_REPS}][{2 * C}] int64 replica rows")
     for name, t in (("dy", dy), ("dx", dx), ("gate", gate), ("g_out", g_out)):
         if t is not None and t.numel() < x.numel():
             raise ValueError(f"bn2d_bwd: {name} smaller than x")
-    call("ttmi_bn2d_bwd", M, C, _p(dy), _p(gate), _p(x), _p(mean), _p(rstd), _p(w), _p(sums),
+    call("ttmi_bn2d_bwd_f32" if f32 else "ttmi_bn2d_bwd", M, C, _p(dy), _p(gate), _p(x), _p(mean), _p(rstd), _p(w), _p(sums),
          _p(g_out), _p(dx), _p(dw), _p(db), _s())
     return dx
 
@@ -745,36 +767,41 @@ def bn2d_bwd_apply(g: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, w: Tensor, 
     (conv2d(..., bn=...)): dx = w·rstd·(g − Σg/M − x̂·Σgx̂/M); dw, db += the sums."""
     C = x.shape[-1]
     M = x.numel() // C
+    f32 = _act_f32("bn2d_bwd_apply", g, x, dx)
     if sums.numel() < 2 * CONV_STAT_REPS * C or sums.dtype != torch.int64:
         raise ValueError(f"bn2d_bwd_apply: sums needs [{CONV_STAT_REPS}][{2 * C}] int64 replica rows")
     if g.numel() < x.numel() or dx.numel() < x.numel():
         raise ValueError("bn2d_bwd_apply: g / dx smaller than x")
-    call("ttmi_bn2d_bwd_apply", M, C, _p(g), None, _p(x), _p(mean), _p(rstd), _p(w), _p(sums), _p(dx),
+    call("ttmi_bn2d_bwd_apply_f32" if f32 else "ttmi_bn2d_bwd_apply", M, C, _p(g), None, _p(x), _p(mean), _p(rstd), _p(w), _p(sums), _p(dx),
          _p(dw), _p(db), _s())
     return dx
 
 
 def maxpool_fwd(x: Tensor, k: int, stride: int, pad: int, y: Tensor, idx: Tensor) -> Tensor:
     N, H, W, C = x.shape
-    call("ttmi_maxpool_fwd", N, H, W, C, k, stride, pad, _p(x), _p(y), _p(idx), _s())
+    f32 = _act_f32("maxpool_fwd", x, y)
+    call("ttmi_maxpool_fwd_f32" if f32 else "ttmi_maxpool_fwd", N, H, W, C, k, stride, pad, _p(x), _p(y), _p(idx), _s())
     return y
 
 
 def maxpool_bwd(dy: Tensor, idx: Tensor, k: int, stride: int, pad: int, dx: Tensor) -> Tensor:
     N, H, W, C = dx.shape
-    call("ttmi_maxpool_bwd", N, H, W, C, k, stride, pad, _p(dy), _p(idx), _p(dx), _s())
+    f32 = _act_f32("maxpool_bwd", dy, dx)
+    call("ttmi_maxpool_bwd_f32" if f32 else "ttmi_maxpool_bwd", N, H, W, C, k, stride, pad, _p(dy), _p(idx), _p(dx), _s())
     return dx
 
 
 def avgpool_fwd(x: Tensor, y: Tensor) -> Tensor:
     N, H, W, C = x.shape
-    call("ttmi_avgpool_fwd", N, H * W, C, _p(x), _p(y), _s())
+    f32 = _act_f32("avgpool_fwd", x, y)
+    call("ttmi_avgpool_fwd_f32" if f32 else "ttmi_avgpool_fwd", N, H * W, C, _p(x), _p(y), _s())
     return y
 
 
 def avgpool_bwd(dy: Tensor, dx: Tensor, gate: Optional[Tensor] = None) -> Tensor:
     N, H, W, C = dx.shape
-    call("ttmi_avgpool_bwd", N, H * W, C, _p(dy), code(dy.dtype), _p(gate), _p(dx), _s())
+    f32 = _act_f32("avgpool_bwd", dx, gate)       # dy [N, C] carries its own dtype code
+    call("ttmi_avgpool_bwd_f32" if f32 else "ttmi_avgpool_bwd", N, H * W, C, _p(dy), code(dy.dtype), _p(gate), _p(dx), _s())
     return dx
 
 

@@ -427,6 +427,9 @@ class TrainStep:
                 return {k[len(pre):]: v for k, v in d.items() if k.startswith(pre)}
             self.enc = [(sub(self.Pi, pre), sub(self.Gi, pre), sub(self.bufs, pre), c)
                         for pre, c in self.RAW_ENCODERS]
+            # each encoder's storage dtype (cnn.py: bf16, or fp32 for reference parity)
+            self.enc_dtypes = [it.audio_encoder.backbone.dtype, it.visual_encoder.backbone.dtype]
+            self.tab_dtype = it.tabular_encoder.dtype
             pre = "tabular_encoder."
             self.tab = (sub(self.Pi, pre), sub(self.Gi, pre), sub(self.bufs, pre))
             self.text = None
@@ -598,13 +601,13 @@ class TrainStep:
         """cfg 3 item encoders (item_tower.py:131-147): audio/visual ResNet-18, zero text slot,
         tabular MLP, concatenated in the reference's order."""
         outs, saved = [], []
-        for (P, _, bufs, c), key in zip(self.enc, ("target_audio", "target_image")):
-            o, st = cnn.resnet18_fwd(P, b[key], c, bufs)
+        for (P, _, bufs, c), key, dt in zip(self.enc, ("target_audio", "target_image"), self.enc_dtypes):
+            o, st = cnn.resnet18_fwd(P, b[key], c, bufs, dtype=dt)
             outs.append(o)
             saved.append(st)
         B = outs[0].shape[0]
         P, _, bufs = self.tab
-        t, tst = cnn.tabular_fwd(P, b["target_tabular"], bufs, seeds, self.p_tab)
+        t, tst = cnn.tabular_fwd(P, b["target_tabular"], bufs, seeds, self.p_tab, dtype=self.tab_dtype)
         xst = ts = None
         if self.text is not None:
             enc, TP, _ = self.text

@@ -96,7 +96,11 @@ class TwoTowerModel(nn.Module):
                  tabular_dim: int = 128, use_lora: bool = True, temperature: float = 0.07, *,
                  compute_dtype: torch.dtype = torch.bfloat16,
                  precomputed_modalities: bool = False, with_text: bool = True,
-                 text_cfg=None, global_negatives: bool = False, process_group=None):
+                 text_cfg=None, global_negatives: bool = False, process_group=None,
+                 encoder_dtype: torch.dtype = torch.bfloat16):
+        """encoder_dtype: activation storage of the raw audio / visual / tabular item encoders
+        (torch.float32: the reference's un-autocast numerics for indexing and evaluation);
+        independent of compute_dtype, which keeps its meaning (user tower and fusion head)."""
         super().__init__()
         self.global_negatives = global_negatives   # cfg 5: negatives from every rank's batch
         self.process_group = process_group
@@ -112,7 +116,7 @@ class TwoTowerModel(nn.Module):
             audio_dim=audio_dim, visual_dim=visual_dim, text_model_name=text_model_name,
             text_dim=text_dim, tabular_dim=tabular_dim, use_lora=use_lora,
             precomputed_modalities=precomputed_modalities, with_text=with_text,
-            text_cfg=text_cfg, compute_dtype=compute_dtype)
+            text_cfg=text_cfg, compute_dtype=compute_dtype, encoder_dtype=encoder_dtype)
 
     def _item(self, batch: Dict[str, Tensor], seeds: Optional[Tensor] = None) -> Tensor:
         if "target_modal" in batch:
