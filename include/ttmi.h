@@ -128,7 +128,16 @@ typedef struct {
 } ttmi_wgrad_desc;
 int64_t ttmi_wgrad_workspace(int64_t R, int64_t M, int64_t N, int64_t ld_dy, int64_t ld_x);
 int ttmi_wgrad(const ttmi_wgrad_desc* d, hipStream_t stream);
-/* Generic split fold: C[m*ldc + n] (+)= Σ_{s < S, in order} part[s*s_stride + m*N + n].
+/* Generic split fold: C[m*ldc + n] (+)= Σ_{s < S} part[s*s_stride + m*N + n]; the sum is formed
+ * first, then added to the previous C in one fp32 add.  Order of the sum (what is guaranteed):
+ *   int64 partials (fx_shift > 0), any S: the exact integer total, converted once,
+ *     float(double(Σq)·2^-fx_shift);
+ *   fp32 partials, S <= 16: sequential fp32 adds in split order s = 0..S-1;
+ *   fp32 partials, S > 16: the splits are cut into P contiguous partitions (P = 4 up to S = 32,
+ *     16 beyond; partition q holds [S·q/P, S·(q+1)/P)), each summed in split order and the P
+ *     sums added in partition order.  A fixed order for a given S, so two runs agree bit for
+ *     bit, but not the S <= 16 order: only |C - Σ| <= 2e-6·Σ|part| is promised against the
+ *     exact sum.
  * accumulate: bit 0 = add to C (else overwrite); bit 1 (ABI 15) = zero the partials read
  * (a workspace that must be zero on the next use, e.g. ttmi_seq_embed_bwd's).
  * fx_shift (ABI 16): 0 = fp32 partials; > 0 = int64 fixed-point partials (value = q·2^-fx_shift,
@@ -155,7 +164,8 @@ int ttmi_wgrad_batch(int n, const ttmi_wgrad_desc* const* descs, int nf,
  * ttmi_adamw_folded is ttmi_adamw_fx that sums each planned segment in the fold's order and
  * applies AdamW to it in the same launch (one process: nothing reads the folded gradient in
  * between).  The partials' workspaces must stay alive and unmodified until it has run; a plan
- * whose segments do not tile the flat buffer in float4 units folds first, then updates. */
+ * whose segments do not tile the flat buffer in float4 units folds first, then updates.  The
+ * fixed-point range is checked as in ttmi_adamw_fx, before anything is folded. */
 typedef struct ttmi_fold_plan {
   int32_t n, reserved;
   uint64_t seg[32 * 16];           /* opaque */
@@ -671,6 +681,8 @@ int ttmi_avgpool_bwd_f32(int N, int HW, int C, const void* dy, int dy_dtype, con
  * Fused AdamW over flat fp32 buffers (torch.optim.AdamW defaults, train.py:302):
  *   t = ++(*step); p *= 1 - lr*wd; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g²;
  *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
+ * m and v are formed in the rounding order of torch's own kernels (lerp_ as one fma, mul_(b2)
+ * rounded before addcmul_), so they equal torch's float32 result bit for bit.
  * hyper (device, fp64) = {lr, beta1, beta2, eps, weight_decay}; step (device int32) holds
  * t (the caller increments it with ttmi_step_inc before the update), so a captured graph
  * replays with the live step count and learning rate.  zero_grad != 0 also clears g after

@@ -195,8 +195,12 @@ TTMI_DEV AdamScalars adam_scalars(const double* hyper, const int32_t* step) {
 TTMI_DEV void adam_upd(const AdamScalars& a, float& P, float G, float& Mv, float& Vv) {
 #pragma clang fp contract(off)
   P = P * a.decay;
-  Mv = fmaf(a.b1c, G - Mv, Mv);                   // exp_avg.lerp_(grad, 1-beta1)
-  Vv = fmaf(Vv, a.b2, a.b2c * (G * G));           // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
+  // The moments in the rounding order of torch's own kernels, so m and v agree with
+  // torch.optim.AdamW bit for bit: lerp_ is fma(w, g - m, m) for a weight below 0.5 and
+  // fma(w - 1, g - m, g) from there on; mul_(b2) rounds before addcmul_ adds ((1-b2)·g)·g.
+  const float d = G - Mv;
+  Mv = fabsf(a.b1c) < 0.5f ? fmaf(a.b1c, d, Mv) : fmaf(a.b1c - 1.0f, d, G);   // exp_avg.lerp_(grad, 1-beta1)
+  Vv = fmaf(a.b2c * G, G, Vv * a.b2);             // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
   const float denom = sqrtf(Vv) / a.bc2_sqrt + a.eps;
   P = fmaf(-a.step_size, Mv / denom, P);
 }

@@ -1626,34 +1626,43 @@ struct FoldArgs { FoldSeg seg[FOLD_SEGS]; int blk_begin[FOLD_SEGS + 1]; int n; i
 // dynamically would put it in scratch memory.
 typedef const __attribute__((address_space(4))) FoldArgs* KFoldArgs;
 
-// The S partials of one 4-column unit, summed in split order: fp32 partials in float, int64
-// fixed-point partials exactly (integer adds) and converted once.  `consume` zeroes them.
+// The int64 fixed-point partials [s_lo, s_hi) of one 4-column unit, added into q: integer adds,
+// exact in any order.  `consume` zeroes them.
+TTMI_DEV void fold_unit_fx(const FoldSeg& sg, int64_t off, int s_lo, int s_hi, bool consume, long long (&q)[4]) {
+  const int64_t* p = static_cast<const int64_t*>(sg.part) + off;
+  for (int s0 = s_lo; s0 < s_hi; s0 += 4) {
+    longlong2 w[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int s = min(s0 + j, s_hi - 1);     // clamped: unconditional loads
+      w[j][0] = *reinterpret_cast<const longlong2*>(p + s * sg.s_stride);
+      w[j][1] = *reinterpret_cast<const longlong2*>(p + s * sg.s_stride + 2);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (s0 + j < s_hi) {
+        q[0] += w[j][0].x; q[1] += w[j][0].y; q[2] += w[j][1].x; q[3] += w[j][1].y;
+        if (consume) {
+          int64_t* z = const_cast<int64_t*>(p) + (s0 + j) * sg.s_stride;
+          *reinterpret_cast<longlong2*>(z) = make_longlong2(0, 0);
+          *reinterpret_cast<longlong2*>(z + 2) = make_longlong2(0, 0);
+        }
+      }
+  }
+}
+
+TTMI_DEV float4 fx_to_f4(const long long (&q)[4], int shift) {
+  return make_float4(fx_to_f(q[0], shift), fx_to_f(q[1], shift), fx_to_f(q[2], shift), fx_to_f(q[3], shift));
+}
+
+// The partials [s_lo, s_hi) of one 4-column unit, summed in split order: fp32 partials in float,
+// int64 fixed-point partials exactly and converted once.  `consume` zeroes them.
 TTMI_DEV float4 fold_unit(const FoldSeg& sg, int64_t off, int s_lo, int s_hi, bool consume) {
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (sg.fx) {
-    const int64_t* p = static_cast<const int64_t*>(sg.part) + off;
     long long q[4] = {0, 0, 0, 0};
-    for (int s0 = s_lo; s0 < s_hi; s0 += 4) {
-      longlong2 w[4][2];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int s = min(s0 + j, s_hi - 1);     // clamped: unconditional loads
-        w[j][0] = *reinterpret_cast<const longlong2*>(p + s * sg.s_stride);
-        w[j][1] = *reinterpret_cast<const longlong2*>(p + s * sg.s_stride + 2);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (s0 + j < s_hi) {
-          q[0] += w[j][0].x; q[1] += w[j][0].y; q[2] += w[j][1].x; q[3] += w[j][1].y;
-          if (consume) {
-            int64_t* z = const_cast<int64_t*>(p) + (s0 + j) * sg.s_stride;
-            *reinterpret_cast<longlong2*>(z) = make_longlong2(0, 0);
-            *reinterpret_cast<longlong2*>(z + 2) = make_longlong2(0, 0);
-          }
-        }
-    }
-    v = make_float4(fx_to_f(q[0], sg.fx), fx_to_f(q[1], sg.fx), fx_to_f(q[2], sg.fx), fx_to_f(q[3], sg.fx));
-    return v;
+    fold_unit_fx(sg, off, s_lo, s_hi, consume, q);
+    return fx_to_f4(q, sg.fx);
   }
   const float* p = static_cast<const float*>(sg.part) + off;
   if (s_hi <= s_lo) return v;
@@ -1691,7 +1700,9 @@ TTMI_DEV void fold_store(const FoldSeg& sg, int64_t u, int64_t nq, float4 v) {
 // split order, the P partition sums are added in partition order through LDS (deterministic
 // for a given S).  P = 4 for a weight gradient's ~12 splits; P = 16 for the many-partial
 // slabs (a LayerNorm's per-workgroup column sums, S ~ 229, 32-64 units), where 4 partitions
-// meant ~57 dependent loads per thread in 4 serial batches.
+// meant ~57 dependent loads per thread in 4 serial batches.  Fixed-point partials keep their
+// partition sums in int64 through LDS and convert the total once (the LayerNorm-backward's 32
+// replica rows): P conversions added in float would round P times.
 constexpr int FOLD_WIDE_S = 32;
 // Up to FOLD_NARROW_S partials (a weight gradient's ~14 splits) a thread owns whole units and
 // sums all their partials itself, in split order: the partitioned form left 3 of 4 threads idle
@@ -1706,35 +1717,56 @@ static_assert(FOLD_NARROW_S < FOLD_WIDE_S, "fold regimes");
 // wgrad_fold_kernel stores them into the gradient, adamw_fold_kernel updates the parameters.
 template <int P, class S4, class S1>
 TTMI_DEV void fold_parts(const FoldSeg& sg, int bx, int nbx, bool consume, int64_t nel, int64_t nq,
-                         S4& store4, S1& store1) {
+                         float4* red, S4& store4, S1& store1) {
   constexpr int U = 256 / P;
-  __shared__ float4 red[256];
+  longlong2* const redq = reinterpret_cast<longlong2*>(red);   // fixed point: two slots a thread
+  const bool fxp = sg.fx != 0;                                  // (no bias rows: units == nel)
   const int ul = threadIdx.x % U, q = threadIdx.x / U;
   const int s_lo = (int)((int64_t)sg.S * q / P), s_hi = (int)((int64_t)sg.S * (q + 1) / P);
   for (int64_t ub = (int64_t)bx * U; ub < sg.units; ub += (int64_t)nbx * U) {
     const int64_t u = ub + ul;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (u < nel) {
-      const int64_t m = u / nq, n = (u % nq) * 4;
-      v = fold_unit(sg, m * sg.N + n, s_lo, s_hi, consume);
-    } else if (u < sg.units) {
-      const int64_t m = u - nel;
-      for (int s0 = s_lo; s0 < s_hi; s0 += 8) {
-        float w[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = sg.part_rs[min(s0 + j, s_hi - 1) * sg.M + m];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (s0 + j < s_hi) v.x += w[j];
+    if (fxp) {
+      long long qs[4] = {0, 0, 0, 0};
+      if (u < nel) {
+        const int64_t m = u / nq, n = (u % nq) * 4;
+        fold_unit_fx(sg, m * sg.N + n, s_lo, s_hi, consume, qs);
       }
+      redq[2 * (q * U + ul)] = make_longlong2(qs[0], qs[1]);
+      redq[2 * (q * U + ul) + 1] = make_longlong2(qs[2], qs[3]);
+    } else {
+      if (u < nel) {
+        const int64_t m = u / nq, n = (u % nq) * 4;
+        v = fold_unit(sg, m * sg.N + n, s_lo, s_hi, consume);
+      } else if (u < sg.units) {
+        const int64_t m = u - nel;
+        for (int s0 = s_lo; s0 < s_hi; s0 += 8) {
+          float w[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) w[j] = sg.part_rs[min(s0 + j, s_hi - 1) * sg.M + m];
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (s0 + j < s_hi) v.x += w[j];
+        }
+      }
+      red[q * U + ul] = v;
     }
-    red[q * U + ul] = v;
     __syncthreads();
     if (q == 0 && u < sg.units) {
+      if (fxp) {              // the integer total of the P partition sums, converted once
+        long long qs[4] = {0, 0, 0, 0};
+#pragma unroll 1
+        for (int k = 0; k < P; ++k) {
+          const longlong2 w0 = redq[2 * (k * U + ul)], w1 = redq[2 * (k * U + ul) + 1];
+          qs[0] += w0.x; qs[1] += w0.y; qs[2] += w1.x; qs[3] += w1.y;
+        }
+        v = fx_to_f4(qs, sg.fx);
+      } else {
 #pragma unroll
-      for (int k = 1; k < P; ++k) {
-        const float4 w = red[k * U + ul];
-        v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
+        for (int k = 1; k < P; ++k) {
+          const float4 w = red[k * U + ul];
+          v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
+        }
       }
       if (u < nel) store4(u, v);
       else store1(u - nel, v.x);
@@ -1768,8 +1800,9 @@ TTMI_DEV void fold_segment(const FoldSeg& sg, int bx, int nbx, S4& store4, S1& s
     }
     return;
   }
-  if (sg.S > FOLD_WIDE_S) fold_parts<16>(sg, bx, nbx, consume, nel, nq, store4, store1);
-  else fold_parts<4>(sg, bx, nbx, consume, nel, nq, store4, store1);
+  __shared__ float4 red[512];   // a float4 a thread; fixed-point partials: its four int64 sums
+  if (sg.S > FOLD_WIDE_S) fold_parts<16>(sg, bx, nbx, consume, nel, nq, red, store4, store1);
+  else fold_parts<4>(sg, bx, nbx, consume, nel, nq, red, store4, store1);
 }
 
 // The last k < n with begin[k] <= b, by binary search over a kernel-argument array (dependent
@@ -3077,6 +3110,12 @@ extern "C" int ttmi_adamw_folded_skip(int64_t n, float* p, float* g, float* m, f
   TTMI_REQUIRE(skip_len == 0 || (!fx && skip_off >= 0 && skip_len > 0 && skip_off % 4 == 0 && skip_len % 4 == 0 &&
                                  skip_off + skip_len <= n),
                "ttmi_adamw_folded_skip: the skipped range must be float4-aligned, inside [0, n), without fx");
+  // ttmi_adamw_fx's own check, made before any fold is launched (the fused form below never
+  // reaches it, and the fallbacks would refuse only after folding)
+  TTMI_REQUIRE(!fx || (fx_off >= 0 && fx_len >= 0 && fx_off % 4 == 0 && fx_len % 4 == 0 &&
+                       fx_off + fx_len <= n - n % 4 && ((uintptr_t)fx & 15) == 0 &&
+                       fx_shift > 0 && fx_shift < 63),
+               "ttmi_adamw_folded: the fixed-point range must be float4-aligned, inside [0, n)");
   if (skip_len > 0 && (!plan || plan->n <= 0 || n % 4 != 0)) {   // the plain update around it
     int rc = plan && plan->n > 0 ? launch_fold_segs(reinterpret_cast<const FoldSeg*>(plan->seg), plan->n, s) : 0;
     if (rc) return rc;
